@@ -31,7 +31,12 @@ An N > 1 line proves itself and carries its own like-for-like baseline:
 At N = 1 `value` is ONE sample per launch (as the reference runs samples: run_YACHT.py:150); `value_batched` is the same
 runner on the whole database -- what N > 1 values are to be divided by.
 
-Rank 0 prints ONE JSON line (contract in the task statement).  Beside the contract's keys:
+A plain run sets up, warms up, times exactly --steps steps and prints the line (`value`, `ms_per_step` = milliseconds of one
+timed step); --dump-outputs DIR writes the counts of the last timed step as DIR/{overlap,n_exclusive,n_matches}.npy (float64,
+one entry per reference: the same arguments give the same inputs, so two builds compare output for output).  Everything
+else runs only with --full.
+
+Rank 0 prints ONE JSON line (contract in the task statement).  Beside the contract's keys, with --full:
   device_resident   median / p10 / p90 of per-step HIP-event intervals (a separate pass)
   host_inclusive    SURVEY.md 8d's metric: pinned sample -> H2D -> kernels -> counts D2H, pipelined
                     (yh_run_submit / yh_run_wait), + the latency of one synchronous yh_run call
@@ -109,10 +114,18 @@ def parse_args():
                          "exchange) instead of the ranks' non-zero (word, reference) entries")
     ap.add_argument("--no-same-form", action="store_true",
                     help="N>1: skip rank 0's single-GPU pass of the same form on the same samples (value_1gpu_same_form, scaling_efficiency)")
-    ap.add_argument("--min-timed-steps", type=int, default=2000,
-                    help="the timed loop runs max(--steps, this) steps, and more until it lasts --min-timed-ms (SURVEY.md 8d: >= 1000 "
-                         "iterations on launch-bound configurations; 20 steps are 0.75 ms of timed region)")
-    ap.add_argument("--min-timed-ms", type=float, default=50.0)
+    ap.add_argument("--min-timed-steps", type=int, default=0,
+                    help="off by default (--steps is the number of timed steps): the timed loop runs max(--steps, this) steps, and more "
+                         "until it lasts --min-timed-ms; --full: the real_shape leg runs max(--steps, this, 2000) steps")
+    ap.add_argument("--min-timed-ms", type=float, default=0.0)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: percentiles, the other lookup paths, host-inclusive, real-shape, batched and "
+                         "scaling-model legs, roofline, CPU baseline + parity against the oracle, the train and sketch children; N > 1: "
+                         "the distributed proof and the single-GPU pass of the same form.  Without it a run sets up, warms up, times "
+                         "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the counts of the timed loop's last step (overlap, n_exclusive, n_matches per "
+                         "reference) as DIR/<name>.npy in float64")
     ap.add_argument("--pack-threads", default="2,4,8,16,24,32", help="host-inclusive leg with yh_sample_pack INSIDE the step: packing threads to try")
     ap.add_argument("--sync-gather", action="store_true", help="N>1: blocking gather of the count rows inside every step")
     ap.add_argument("--count-gather", choices=("root", "all"), default="root",
@@ -207,6 +220,10 @@ def cpu_model() -> str:
 def main() -> int:
     args = parse_args()
     args.pipelined_tail = not args.plain_steps
+    if not args.full:  # a plain run measures the headline only: every leg with a switch of its own is off
+        for leg in ("no_host_inclusive", "no_real_shape", "no_batched", "no_scaling_model", "no_cpu_baseline", "no_train",
+                    "no_sketch", "no_same_form"):
+            setattr(args, leg, True)
     wall = {}  # this process's wall-clock by section (seconds): a slow box or a driver stall shows up here
     t_wall = [time.perf_counter()]
 
@@ -498,23 +515,22 @@ def main() -> int:
     drain()
     fence()
     db.timing()  # drop the warm-up launches from the kernel-duration ring
-    # How many steps the timed region holds: --steps as the driver passes it is a handful (20 steps = 0.75 ms of timed region:
-    # +-7 % from run to run), so the loop runs max(--steps, --min-timed-steps) steps -- and, should that still be shorter
-    # than --min-timed-ms, as many as a short calibration pass says it takes (the same number on every rank).
+    # How many steps the timed region holds: --steps.  Only a caller who asks for it (--min-timed-steps, --min-timed-ms) gets a
+    # longer loop: max(--steps, --min-timed-steps) steps and, should that be shorter than --min-timed-ms, as many as a short
+    # calibration pass says it takes (the same number on every rank).
     n_timed = max(args.steps, args.min_timed_steps)
-    n_cal = max(min(n_timed, 256), BB if hash_batched else 1)
-    t0 = time.perf_counter()
-    for _ in range(n_cal):
-        step()
-    drain()
-    fence()
-    cal = torch.tensor([(time.perf_counter() - t0) / n_cal], device=dev, dtype=torch.float64)
-    if multi:
-        cal = ydist._stage(cal, None)
-        dist.all_reduce(cal, op=dist.ReduceOp.MAX)
-    n_timed = max(n_timed, int(math.ceil(args.min_timed_ms * 1e-3 / max(float(cal.item()), 1e-9))))
-    if hash_batched:
-        n_timed = ((n_timed + BB - 1) // BB) * BB  # whole blocks
+    if args.min_timed_ms > 0:
+        n_cal = max(min(n_timed, 256), BB if hash_batched else 1)
+        t0 = time.perf_counter()
+        for _ in range(n_cal):
+            step()
+        drain()
+        fence()
+        cal = torch.tensor([(time.perf_counter() - t0) / n_cal], device=dev, dtype=torch.float64)
+        if multi:
+            cal = ydist._stage(cal, None)
+            dist.all_reduce(cal, op=dist.ReduceOp.MAX)
+        n_timed = max(n_timed, int(math.ceil(args.min_timed_ms * 1e-3 / max(float(cal.item()), 1e-9))))
     db.timing()
     # (HIP events on the handle's stream around the launches of the timed region -- the roofline's launch duration when a
     # step is ONE launch: see `duration_basis` below)
@@ -524,6 +540,7 @@ def main() -> int:
     for _ in range(n_timed):
         step()
     t_issued = time.perf_counter() - t0  # host time to QUEUE the steps (no waiting): host-bound when it equals `elapsed`
+    i_last = state["i"] - 1  # (drain() below rounds the step counter of a multi-GPU loop up to a whole block)
     ev_region[1].record(stream)
     drain()
     fence()
@@ -535,53 +552,74 @@ def main() -> int:
     ms_per_step = 1e3 * elapsed / n_timed
     value = n_total / (elapsed / n_timed)
 
-    stamp("database_and_timed_region")
-    # ---- per-step percentiles: a separate pass with one HIP event between steps -------------------------
-    n_pct = max(args.percentile_steps, args.steps)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_pct + 1)]
-    evs[0].record(stream)
-    for k in range(n_pct):
-        step()
-        evs[k + 1].record(stream)
-    drain()
-    fence()
-    step_ms = [evs[k].elapsed_time(evs[k + 1]) for k in range(n_pct)]
-    device_resident = dict(stats_ms(step_ms), how="HIP-event interval per step, separate pass of rotating samples; "
-                                                   "`value`/`ms_per_step` come from the un-instrumented timed loop")
-    timing = db.timing()  # kernel-duration ring: every 32nd launch of the timed region + percentile pass
+    # ---- --dump-outputs: the counts of the timed loop's LAST step as a caller receives them (on rank 0: the rows of the whole
+    # database), copied out before anything else runs on the step buffers
+    if args.dump_outputs and rank == 0:
+        if hash_batched:  # the totals of the block finished last; its last sample is the last step
+            _jl, n_last, rows_l, dense_l = state["last_result"]
+            got = dense_l if rows_l is None else ydist.BatchRowsReducer.rows_to_dense(rows_l, n_last, n_total)
+            last_counts = got[:, n_last - 1, :]
+        elif multi and not by_hash:  # every rank's rows of its own references, in reference order
+            g_all = gathered_blk[(i_last // GB) % NBUF]
+            last_counts = torch.cat([g_all[r, i_last % GB, :, : e_ - b_] for r, (b_, e_) in enumerate(sdb.plan)], dim=1)
+        else:  # N = 1, or the hash-range steps (the block's rows were summed to rank 0)
+            last_counts = rows_of(i_last)[:, :n_total]
+        dumped = last_counts.cpu().numpy().view(np.uint32).astype(np.float64)  # (the library's uint32 counts in int32 tensors)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k_, name_ in enumerate(("overlap", "n_exclusive", "n_matches")):
+            np.save(os.path.join(args.dump_outputs, name_ + ".npy"), dumped[k_])
+        del last_counts, dumped
 
-    # last step's counts of every sample (for parity): run each sample once more into its own buffer
+    stamp("database_and_timed_region")
+    device_resident = None
     results = []
-    for i in range(K):
-        c = torch.zeros((3, row_stride), device=dev, dtype=torch.int32)
-        with torch.cuda.stream(stream):
-            if sdb is None:
-                db.run_device(samples[i].data_ptr(), samples[i].numel(), c[0].data_ptr(), c[1].data_ptr(), c[2].data_ptr())
-                results.append(c)
-            else:
-                sdb.run(samples[i], c)
-                results.append(sdb.gather(c))
-    torch.cuda.synchronize()
-    blocks_ok = None
-    if hash_batched and rank == 0:  # the timed loop's own outputs: the totals of the block finished last are on rank 0
-        jl, n_last, rows_l, dense_l = state["last_result"]
-        got = dense_l if rows_l is None else ydist.BatchRowsReducer.rows_to_dense(rows_l, n_last, n_total)
-        blocks_ok = all(bool(torch.equal(got[:, t, :], results[((jl * BB) % K + t) % K])) for t in range(n_last))
-    pipelined_ok = None
-    if sdb is None and args.pipelined_tail:  # the timed loop's own (pipelined) outputs: its last two steps are still in the buffers
-        last = state["i"] - 1
-        pipelined_ok = all(bool(torch.equal(rows_of(last - d), results[(last - d) % K])) for d in range(min(2, NBUF)))
-    if multi and not by_hash:  # the steps' own gathers must carry this rank's rows
-        for b in range(NBUF):
-            if not to_root or rank == 0:
-                assert bool(torch.equal(gathered_blk[b][rank], counts_blk[b])), "gather ran ahead of the kernels"
+    blocks_ok = pipelined_ok = None
+    if not args.full:
+        timing = db.timing()  # (db_build_ms of the line)
+    else:
+        # ---- per-step percentiles: a separate pass with one HIP event between steps -------------------------
+        n_pct = max(args.percentile_steps, args.steps)
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_pct + 1)]
+        evs[0].record(stream)
+        for k in range(n_pct):
+            step()
+            evs[k + 1].record(stream)
+        drain()
+        fence()
+        step_ms = [evs[k].elapsed_time(evs[k + 1]) for k in range(n_pct)]
+        device_resident = dict(stats_ms(step_ms), how="HIP-event interval per step, separate pass of rotating samples; "
+                                                       "`value`/`ms_per_step` come from the un-instrumented timed loop")
+        timing = db.timing()  # kernel-duration ring: every 32nd launch of the timed region + percentile pass
+
+        # last step's counts of every sample (for parity): run each sample once more into its own buffer
+        for i in range(K):
+            c = torch.zeros((3, row_stride), device=dev, dtype=torch.int32)
+            with torch.cuda.stream(stream):
+                if sdb is None:
+                    db.run_device(samples[i].data_ptr(), samples[i].numel(), c[0].data_ptr(), c[1].data_ptr(), c[2].data_ptr())
+                    results.append(c)
+                else:
+                    sdb.run(samples[i], c)
+                    results.append(sdb.gather(c))
+        torch.cuda.synchronize()
+        if hash_batched and rank == 0:  # the timed loop's own outputs: the totals of the block finished last are on rank 0
+            jl, n_last, rows_l, dense_l = state["last_result"]
+            got = dense_l if rows_l is None else ydist.BatchRowsReducer.rows_to_dense(rows_l, n_last, n_total)
+            blocks_ok = all(bool(torch.equal(got[:, t, :], results[((jl * BB) % K + t) % K])) for t in range(n_last))
+        if sdb is None and args.pipelined_tail:  # the timed loop's own (pipelined) outputs: its last two steps are still in the buffers
+            last = state["i"] - 1
+            pipelined_ok = all(bool(torch.equal(rows_of(last - d), results[(last - d) % K])) for d in range(min(2, NBUF)))
+        if multi and not by_hash:  # the steps' own gathers must carry this rank's rows
+            for b in range(NBUF):
+                if not to_root or rank == 0:
+                    assert bool(torch.equal(gathered_blk[b][rank], counts_blk[b])), "gather ran ahead of the kernels"
 
     stamp("percentiles")
     # ---- N = 1 extras ------------------------------------------------------------------------------------
     indexed = host_inclusive = real_shape = None
     paths = {}
     default_choice = db.lookup_choice(n_sample)  # (the sharded step asks the same question inside yh_run_local_device)
-    if not multi:
+    if not multi and args.full:
         timing_default = timing
         cpath2 = [torch.zeros((3, n_local), device=dev, dtype=torch.int32) for _ in range(2)]
         cpath = cpath2[0]
@@ -791,7 +829,7 @@ def main() -> int:
         fence_real()
         db.timing()
         ev2 = [torch.cuda.Event(enable_timing=True) for _ in range(n_pct + 1)]
-        n_real = max(args.steps, args.min_timed_steps)  # (a 20-step loop is 0.3 ms: anything the host does is in it)
+        n_real = max(args.steps, args.min_timed_steps, 2000)  # (a 20-step loop is 0.3 ms: anything the host does is in it)
         t0 = time.perf_counter()
         for i in range(n_real):
             step_real(i)
@@ -1034,7 +1072,7 @@ def main() -> int:
     #                           (all-gathered) and a one-word all-reduce whose answer only N distinct ranks can produce
     same_form = None
     dist_proof = None
-    if multi:
+    if multi and args.full:
         ident = {"rank": rank, "local_rank": local_rank, "device_index": int(torch.cuda.current_device()), "pid": os.getpid()}
         try:
             pr_ = torch.cuda.get_device_properties(dev)
@@ -1130,77 +1168,79 @@ def main() -> int:
                                "note": "8 B per reference hash as SURVEY.md 8d counts; this kernel reads none of them"},
         }
 
-    k_ms = float(timing["ms_overlap_kernel"])
-    x_ms = float(timing["ms_exclusive_kernels"])
-    k_pairs_ms = k_ms
-    one_launch_per_step = bool(args.pipelined_tail and not multi and default_choice == ylib.YH_LOOKUP_INDEXED)
-    if one_launch_per_step:
-        # The step is ONE launch (k_step_fused), so the launches of the timed region are exactly n_timed and the interval between
-        # two HIP events on their stream, one before the first and one behind the last, divided by n_timed, is the kernel's
-        # average duration INCLUDING the dispatch gaps between consecutive launches -- an upper bound, never flattering -- and
-        # without the ~5 us a per-launch event pair adds to every sampled launch (`kernel_ms_avg_event_pairs`; rocprofv3's
-        # own figure for the kernel is in profiles/: 33.4 us).
-        k_ms = float(ev_region[0].elapsed_time(ev_region[1])) / n_timed
-    rl_main[0] = True
-    roofline = (roofline_indexed if default_choice == ylib.YH_LOOKUP_INDEXED else roofline_stream)(k_ms, x_ms)
-    rl_main[0] = False
-    if roofline["kernel"] == "k_step_fused":
-        roofline["kernel_note"] = ("one launch per step: the lookup of this sample (the role the bytes are counted for: "
-                                   "k_index_lookup_tile's body) + the reducer of the previous sample + the exclusive pass of the one before")
-    roofline["duration_basis"] = (f"HIP events on the handle's stream around the {n_timed} launches of the timed region / {n_timed} "
-                                  "(dispatch gaps included)" if one_launch_per_step else
-                                  "HIP event pairs around every 32nd launch of the dominant kernel in the timed region (the library's ring)")
-    roofline["kernel_ms_avg_event_pairs"] = round(k_pairs_ms, 4)
-    roofline["default_lookup"] = "indexed" if default_choice == ylib.YH_LOOKUP_INDEXED else "stream"
-    # (scalar copies of the nested survey_formula block: parsers that keep only scalars keep these)
-    roofline["bytes_survey_formula"] = roofline["survey_formula"]["bytes_per_launch"]
-    roofline["GBps_survey_formula"] = roofline["survey_formula"]["GBps"]
-    roofline["frac_survey_formula"] = roofline["survey_formula"]["frac"]
-    # What a HIP-event pair measures with NOTHING between its two records, on the busy stream of the step loop: the
-    # part of `kernel_ms_avg` that is marker processing and dispatch, not kernel (rocprofv3's kernel durations in
-    # profiles/ do not contain it).  `achieved` / `frac` stay on the raw interval: never flattered.
-    if not multi:
-        pairs = []
-        for _ in range(64):
-            step()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            e1.record(stream)
-            pairs.append((e0, e1))
-        drain()
-        fence()
-        gaps = sorted(a.elapsed_time(b) for a, b in pairs)
-        empty_ms = float(gaps[len(gaps) // 2])
-        roofline["event_pair_overhead_ms"] = round(empty_ms, 4)
-        roofline["kernel_ms_avg_net_of_event_overhead"] = round(max(k_pairs_ms - empty_ms, 0.0), 4)  # (of the per-launch pairs)
-    other = None
-    if "stream" in paths and default_choice == ylib.YH_LOOKUP_INDEXED:
-        other = roofline_stream(paths["stream"]["lookup_kernel_ms_avg"], paths["stream"]["exclusive_kernels_ms_avg"])
-    elif "indexed" in paths and default_choice == ylib.YH_LOOKUP_STREAM:
-        other = roofline_indexed(paths["indexed"]["lookup_kernel_ms_avg"], paths["indexed"]["exclusive_kernels_ms_avg"])
-    # HBM bytes per launch from the rocprofv3 --pmc passes (profiles/README.md), attached only when they
-    # were taken from THIS source of the kernels on THIS workload; otherwise null.
-    tag = source_tag()
-    for name in sorted(os.listdir(os.path.join(ROOT, "profiles")), reverse=True):
-        if not (name.startswith("traffic_") and name.endswith(".json")):
-            continue
-        try:
-            with open(os.path.join(ROOT, "profiles", name)) as f:
-                tr = json.load(f)
-            for rl in (roofline, other):
-                if rl is not None and rl["traffic"] is None and tr.get("source_tag") == tag and tr.get("n_hashes") == Hh \
-                        and tr.get("kernel") == rl["kernel"]:
-                    rl["traffic"] = tr.get("hbm_bytes_per_launch")
-                    if tr.get("l2_requests_per_launch") and rl.get("kernel_ms_avg"):
-                        # isolated reads are bound by the NUMBER of L2 requests (TCC_REQ, same PMC passes): the rate over
-                        # this run's kernel interval, next to scripts/probes/gather_probe.hip's ceiling for launches of
-                        # 1e6 independent 64-byte reads (3.7e10/s; 4.6e10/s at 1.6e7)
-                        rl["l2_requests_per_launch"] = tr["l2_requests_per_launch"]
-                        rl["l2_requests_per_s"] = round(tr["l2_requests_per_launch"] / (rl["kernel_ms_avg"] / 1e3), 1)
-                    rl["traffic_provenance"] = {"file": "profiles/" + name, "source_tag": tag,
-                                                "taken": tr.get("taken"), "commit": tr.get("commit")}
-        except Exception:
-            pass
+    roofline = other = None
+    if args.full:
+        k_ms = float(timing["ms_overlap_kernel"])
+        x_ms = float(timing["ms_exclusive_kernels"])
+        k_pairs_ms = k_ms
+        one_launch_per_step = bool(args.pipelined_tail and not multi and default_choice == ylib.YH_LOOKUP_INDEXED)
+        if one_launch_per_step:
+            # The step is ONE launch (k_step_fused), so the launches of the timed region are exactly n_timed and the interval between
+            # two HIP events on their stream, one before the first and one behind the last, divided by n_timed, is the kernel's
+            # average duration INCLUDING the dispatch gaps between consecutive launches -- an upper bound, never flattering -- and
+            # without the ~5 us a per-launch event pair adds to every sampled launch (`kernel_ms_avg_event_pairs`; rocprofv3's
+            # own figure for the kernel is in profiles/: 33.4 us).
+            k_ms = float(ev_region[0].elapsed_time(ev_region[1])) / n_timed
+        rl_main[0] = True
+        roofline = (roofline_indexed if default_choice == ylib.YH_LOOKUP_INDEXED else roofline_stream)(k_ms, x_ms)
+        rl_main[0] = False
+        if roofline["kernel"] == "k_step_fused":
+            roofline["kernel_note"] = ("one launch per step: the lookup of this sample (the role the bytes are counted for: "
+                                       "k_index_lookup_tile's body) + the reducer of the previous sample + the exclusive pass of the one before")
+        roofline["duration_basis"] = (f"HIP events on the handle's stream around the {n_timed} launches of the timed region / {n_timed} "
+                                      "(dispatch gaps included)" if one_launch_per_step else
+                                      "HIP event pairs around every 32nd launch of the dominant kernel in the timed region (the library's ring)")
+        roofline["kernel_ms_avg_event_pairs"] = round(k_pairs_ms, 4)
+        roofline["default_lookup"] = "indexed" if default_choice == ylib.YH_LOOKUP_INDEXED else "stream"
+        # (scalar copies of the nested survey_formula block: parsers that keep only scalars keep these)
+        roofline["bytes_survey_formula"] = roofline["survey_formula"]["bytes_per_launch"]
+        roofline["GBps_survey_formula"] = roofline["survey_formula"]["GBps"]
+        roofline["frac_survey_formula"] = roofline["survey_formula"]["frac"]
+        # What a HIP-event pair measures with NOTHING between its two records, on the busy stream of the step loop: the
+        # part of `kernel_ms_avg` that is marker processing and dispatch, not kernel (rocprofv3's kernel durations in
+        # profiles/ do not contain it).  `achieved` / `frac` stay on the raw interval: never flattered.
+        if not multi:
+            pairs = []
+            for _ in range(64):
+                step()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                e1.record(stream)
+                pairs.append((e0, e1))
+            drain()
+            fence()
+            gaps = sorted(a.elapsed_time(b) for a, b in pairs)
+            empty_ms = float(gaps[len(gaps) // 2])
+            roofline["event_pair_overhead_ms"] = round(empty_ms, 4)
+            roofline["kernel_ms_avg_net_of_event_overhead"] = round(max(k_pairs_ms - empty_ms, 0.0), 4)  # (of the per-launch pairs)
+        other = None
+        if "stream" in paths and default_choice == ylib.YH_LOOKUP_INDEXED:
+            other = roofline_stream(paths["stream"]["lookup_kernel_ms_avg"], paths["stream"]["exclusive_kernels_ms_avg"])
+        elif "indexed" in paths and default_choice == ylib.YH_LOOKUP_STREAM:
+            other = roofline_indexed(paths["indexed"]["lookup_kernel_ms_avg"], paths["indexed"]["exclusive_kernels_ms_avg"])
+        # HBM bytes per launch from the rocprofv3 --pmc passes (profiles/README.md), attached only when they
+        # were taken from THIS source of the kernels on THIS workload; otherwise null.
+        tag = source_tag()
+        for name in sorted(os.listdir(os.path.join(ROOT, "profiles")), reverse=True):
+            if not (name.startswith("traffic_") and name.endswith(".json")):
+                continue
+            try:
+                with open(os.path.join(ROOT, "profiles", name)) as f:
+                    tr = json.load(f)
+                for rl in (roofline, other):
+                    if rl is not None and rl["traffic"] is None and tr.get("source_tag") == tag and tr.get("n_hashes") == Hh \
+                            and tr.get("kernel") == rl["kernel"]:
+                        rl["traffic"] = tr.get("hbm_bytes_per_launch")
+                        if tr.get("l2_requests_per_launch") and rl.get("kernel_ms_avg"):
+                            # isolated reads are bound by the NUMBER of L2 requests (TCC_REQ, same PMC passes): the rate over
+                            # this run's kernel interval, next to scripts/probes/gather_probe.hip's ceiling for launches of
+                            # 1e6 independent 64-byte reads (3.7e10/s; 4.6e10/s at 1.6e7)
+                            rl["l2_requests_per_launch"] = tr["l2_requests_per_launch"]
+                            rl["l2_requests_per_s"] = round(tr["l2_requests_per_launch"] / (rl["kernel_ms_avg"] / 1e3), 1)
+                        rl["traffic_provenance"] = {"file": "profiles/" + name, "source_tag": tag,
+                                                    "taken": tr.get("taken"), "commit": tr.get("commit")}
+            except Exception:
+                pass
 
     stamp("roofline")
     # ---- CPU baseline + full-size parity (rank 0, the WHOLE database) -----------------------------------
@@ -1329,11 +1369,13 @@ def main() -> int:
         scaling_efficiency = round(value / (world * value_1gpu_same_form), 4)
     train_di = ((train or {}).get("device_input") or {})
     if rank == 0:
-        try:
-            import scipy
-            scipy_version = scipy.__version__
-        except Exception:
-            scipy_version = None
+        scipy_version = None
+        if args.full:
+            try:
+                import scipy
+                scipy_version = scipy.__version__
+            except Exception:
+                pass
         out = {
             "metric": "ref-sketch containment queries/sec (yacht run)",
             "value": round(value, 1),
@@ -1382,7 +1424,8 @@ def main() -> int:
                 "train_host_input_ms": (round(1e3 * train["seconds"]["total"], 3) if (train or {}).get("seconds") else None),
                 "train_packed_input_ms": (round(1e3 * train["packed_input"]["seconds"]["total"], 3)
                                           if ((train or {}).get("packed_input") or {}).get("seconds") else None),
-                "roofline_frac": roofline.get("frac"), "roofline_kernel_us": round(1e3 * float(roofline.get("kernel_ms_avg") or 0.0), 2),
+                "roofline_frac": (roofline or {}).get("frac"),
+                "roofline_kernel_us": round(1e3 * float(roofline["kernel_ms_avg"]), 2) if roofline else None,
                 "refs_per_gpu": n_local,
                 "ref_hashes_per_gpu": Hh,
                 "sample_hashes": n_sample,
@@ -1448,7 +1491,8 @@ def main() -> int:
         # driver's record unparsed).
         import bench_line
 
-        extras_path = bench_line.write_extras(out, ROOT, args.extras)
+        # (a plain run writes the side file only where --extras names one)
+        extras_path = bench_line.write_extras(out, ROOT, args.extras) if (args.full or args.extras) else None
         sys.stderr.write("bench.py: full result (also in %s):\n%s\n" % (extras_path, json.dumps(out, indent=1, default=str)))
         sys.stderr.flush()
         sys.stdout.flush()

@@ -5,7 +5,7 @@
 # Build first (build container):  for v in 32 64 3 7 15 31 127: build.build_variant('l%d' % v, {'YH_ABLATE_LOOKUP': v}); 'lb': {'YH_LOOKUP_LATE_BAD': 1}
 # usage (GPU box, repo root): bash scripts/ablate_step.sh
 cd "$GRAFT_REPO_ROOT" || exit 1
-B="timeout 300 python bench.py --no-batched --no-cpu-baseline --no-train --no-scaling-model --no-host-inclusive --no-real-shape --steps 300 --percentile-steps 300 --min-timed-steps 4000"
+B="timeout 300 python bench.py --full --no-batched --no-cpu-baseline --no-train --no-scaling-model --no-host-inclusive --no-real-shape --steps 300 --percentile-steps 300 --min-timed-steps 4000"
 P='import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d["roofline"]; print("%-8s %-58s fused step %.4f ms   kernel (events) %.1f us  net of event pair %.1f us   plain lookup kernel %.1f us" % (sys.argv[1], sys.argv[2], d["ms_per_step"], 1e3*r["kernel_ms_avg"], 1e3*r.get("kernel_ms_avg_net_of_event_overhead", 0), 1e3*d["paths"]["indexed"]["lookup_kernel_ms_avg"]))'
 run() {
   v=$1; what=$2

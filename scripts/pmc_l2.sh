@@ -1,7 +1,7 @@
 # usage (GPU box): bash scripts/pmc_l2.sh   -- L2 hit/miss counters of k_stream_lookup
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT" || exit 1
-B="python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-indexed"
+B="python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-indexed"
 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_READ_sum --output-format csv -d gpurun_out/pmcx_l2 -- $B > /dev/null 2>&1
 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum --output-format csv -d gpurun_out/pmcx_l2b -- $B > /dev/null 2>&1
 python3 - <<PY

@@ -12,10 +12,10 @@ for v in 0 1 2 3; do
   for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_REQ_sum TCC_MISS_sum TCC_HIT_sum"; do
     tag=$(echo $grp | cut -d' ' -f1)
     rm -rf /tmp/pmcs_${v}_$tag
-    rocprofv3 --pmc $grp --output-format csv -d /tmp/pmcs_${v}_$tag -- python3 bench.py --steps 20 --warmup 5 --no-train --no-sketch --no-scaling-model --no-cpu-baseline --no-host-inclusive --no-batched --no-real-shape --min-timed-steps 40 --percentile-steps 20 > /dev/null 2>&1
+    rocprofv3 --pmc $grp --output-format csv -d /tmp/pmcs_${v}_$tag -- python3 bench.py --full --steps 20 --warmup 5 --no-train --no-sketch --no-scaling-model --no-cpu-baseline --no-host-inclusive --no-batched --no-real-shape --min-timed-steps 40 --percentile-steps 20 > /dev/null 2>&1
   done
   rm -rf /tmp/pmcs_${v}_trace
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pmcs_${v}_trace -- python3 bench.py --steps 20 --warmup 5 --no-train --no-sketch --no-scaling-model --no-cpu-baseline --no-host-inclusive --no-batched --no-real-shape --min-timed-steps 40 --percentile-steps 20 > /dev/null 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pmcs_${v}_trace -- python3 bench.py --full --steps 20 --warmup 5 --no-train --no-sketch --no-scaling-model --no-cpu-baseline --no-host-inclusive --no-batched --no-real-shape --min-timed-steps 40 --percentile-steps 20 > /dev/null 2>&1
   python3 - $v >> $OUT <<'PY'
 import csv, glob, collections, sys
 v = sys.argv[1]

@@ -2,7 +2,7 @@
 # L2 counters and FETCH_SIZE of k_batch_lookup in runs of their own.  usage (GPU box): bash scripts/profile_batched.sh > gpurun_out/batched_profile.txt
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
-B="python3 bench.py --steps 10 --warmup 2 --min-timed-steps 100 --min-timed-ms 0 --no-cpu-baseline --no-host-inclusive --no-real-shape --no-train --no-scaling-model"
+B="python3 bench.py --full --steps 10 --warmup 2 --min-timed-steps 100 --min-timed-ms 0 --no-cpu-baseline --no-host-inclusive --no-real-shape --no-train --no-scaling-model"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_batch -- $B > gpurun_out/prof_batch.log 2>&1
 timeout 600 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_ATOMIC_sum --output-format csv -d gpurun_out/pmc_batch_tcc -- $B > gpurun_out/pmc_batch_tcc.log 2>&1
 timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_batch_fetch -- $B > gpurun_out/pmc_batch_fetch.log 2>&1

@@ -7,7 +7,7 @@ for u in (1, 2, 4, 8):
     build.build_variant(f"bu{u}", {"YH_BATCH_U": u})
 PY
 for u in 1 2 4 8; do for take in 1 2; do
-  YACHT_HIP_LIB="yacht_amd/lib/libyacht_hip_bu$u.so" python3 bench.py --no-train --no-sketch --no-cpu-baseline --no-host-inclusive --no-real-shape 2>/dev/null | tail -1 > /tmp/line.json
+  YACHT_HIP_LIB="yacht_amd/lib/libyacht_hip_bu$u.so" python3 bench.py --full --no-train --no-sketch --no-cpu-baseline --no-host-inclusive --no-real-shape 2>/dev/null | tail -1 > /tmp/line.json
   python3 - "$u" <<'PY'
 import json, sys
 d = json.loads(open("/tmp/line.json").read())

@@ -9,7 +9,7 @@ for k in (1, 2, 3):
 PY
 run() {  # label, lib, bph
   for take in 1 2 3; do
-  YACHT_HIP_LIB="$2" YH_DEBUG_TUNING=1 YH_FILTER_BPH="$3" python3 bench.py --no-train --no-sketch --no-scaling-model --no-cpu-baseline --no-host-inclusive --no-real-shape --min-timed-steps 4000 2>/dev/null | tail -1 > /tmp/line.json
+  YACHT_HIP_LIB="$2" YH_DEBUG_TUNING=1 YH_FILTER_BPH="$3" python3 bench.py --full --no-train --no-sketch --no-scaling-model --no-cpu-baseline --no-host-inclusive --no-real-shape --min-timed-steps 4000 2>/dev/null | tail -1 > /tmp/line.json
   python3 - "$1" "$3" <<'PY'
 import json, sys
 d = json.loads(open("/tmp/line.json").read())

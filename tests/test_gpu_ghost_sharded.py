@@ -145,7 +145,7 @@ def test_bench_over_rccl_one_rank(hip_lib, shard):
     """bench.py's N > 1 code path (sharded step + async collectives of the bits and the count rows) on RCCL with one rank."""
     env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
                HSA_ENABLE_IPC_MODE_LEGACY="0", YH_FORCE_EXCHANGE="1")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--shard", shard, "--steps", "6", "--min-timed-steps", "0", "--min-timed-ms", "0", "--warmup", "2",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--force-dist", "--shard", shard, "--steps", "6", "--min-timed-steps", "0", "--min-timed-ms", "0", "--warmup", "2",
                         "--refs", "4000", "--sample-hashes", "100000", "--samples", "3", "--percentile-steps", "8", "--present", "50"] + _extras_arg(),
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout + p.stderr
@@ -165,7 +165,7 @@ def test_bench_two_ranks_share_gpu_strong_and_weak(hip_lib, tmp_path, shard):
             env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
                        MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
             procs.append(subprocess.Popen(
-                [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--min-timed-steps", "0", "--min-timed-ms", "0", "--warmup", "2",
+                [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "6", "--min-timed-steps", "0", "--min-timed-ms", "0", "--warmup", "2",
                  "--backend", "gloo", "--share-gpu", "--scaling", scaling, "--shard", shard, "--refs", "4000", "--sample-hashes", "100000",
                  "--samples", "3", "--percentile-steps", "8", "--present", "50", "--batch-block", "4", "--extras", str(tmp_path / f"extras_{scaling}.json")],
                 env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
@@ -194,7 +194,7 @@ def test_bench_two_ranks_share_gpu_strong_and_weak(hip_lib, tmp_path, shard):
 def test_bench_two_ranks_hash_range_single_steps(hip_lib, tmp_path):
     """--block-mode steps: the per-sample half-steps of the hash-range shards (the batched blocks are the default)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--backend", "gloo",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--share-gpu", "--backend", "gloo",
                         "--block-mode", "steps", "--steps", "6", "--min-timed-steps", "0", "--min-timed-ms", "0", "--warmup", "2", "--refs", "4000", "--sample-hashes", "100000",
                         "--samples", "3", "--percentile-steps", "8", "--present", "50"] + _extras_arg(),
                        env=env, capture_output=True, text=True, timeout=900)
@@ -207,7 +207,7 @@ def test_bench_starts_its_own_ranks(hip_lib):
     """`python bench.py --gpus 2 ...` with NO launcher and no WORLD_SIZE, the way the driver starts `--gpus 1`: bench.py
     spawns its two ranks as child processes (before anything touches the GPU) and relays rank 0's line."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--backend", "gloo",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--share-gpu", "--backend", "gloo",
                         "--steps", "6", "--min-timed-steps", "0", "--min-timed-ms", "0", "--warmup", "2", "--refs", "4000", "--sample-hashes", "100000", "--samples", "3",
                         "--percentile-steps", "8", "--present", "50"] + _extras_arg(),
                        env=env, capture_output=True, text=True, timeout=900)
