@@ -379,6 +379,23 @@ int yh_run_batch_rows_pack_device(yh_db* db, int slot, const uint32_t* d_overlap
 int yh_run_batch_rows_unpack_device(yh_db* db, int slot, const uint32_t* d_vals, uint64_t cap_rows, yh_batch_row* d_rows,
                                     uint32_t* d_n_rows);
 
+/* ---- the presence test of a block's compact rows on the device (additive in ABI 8) ----------------------------------------
+ * For every row k < min(*d_n_rows, cap_rows) of d_rows (what yh_run_batch_rows_unpack_device wrote) and every coverage c
+ * (n_covs <= YH_PRESENCE_MAX_COVS), outputs [n_covs][cap_rows] (index c * cap_rows + k):
+ *   d_n_cov[.]   = (uint32_t)((double)n_excl * min_coverage[c])        (yh_hyp_test's n_excl_cov)
+ *   d_p_val[.]   = binom.cdf(n_match, n_cov, ani_thresh ** ksize) if n_match <= n_cov else 1   (yh_hyp_test's p_val, in
+ *                  double on the device: ~1e-12 relative of the host's long double)
+ *   d_present[.] = n_match >= d_thr[n_cov] && n_match != 0
+ * d_thr[0 .. n_max] (device) = the acceptance thresholds by n: one yh_hyp_test over n_excl = 0..n_max, n_match = 0,
+ * min_coverage = 1 gives them, and its confidence / alt. mutation rate columns are the host's table of the other two
+ * columns (gathered by n_cov).  A row whose n_cov exceeds n_max gets p_val NaN and present 0.  min_coverage is a host array.
+ * Enqueued on the handle's stream, no host sync; reads no handle state.  (Reference: single_hyp_test,
+ * hypothesis_recovery_src.py:233-306, once per organism and coverage.)                                               */
+#define YH_PRESENCE_MAX_COVS 16
+int yh_presence_rows_device(yh_db* db, const yh_batch_row* d_rows, const uint32_t* d_n_rows, uint64_t cap_rows, int ksize,
+                            double ani_thresh, const double* min_coverage, uint32_t n_covs, const double* d_thr, uint32_t n_max,
+                            double* d_p_val, uint8_t* d_present, uint32_t* d_n_cov);
+
 /* ---- the subset words of a block in compact form (ABI 5) ----------------------------------------------------------------
  * Between the two halves of a batched hash-range run every rank needs the OR of all ranks' subset words.  The dense row
  * (one uint64 per reference: 8 N bytes per rank and block, 682 KB at rs214 scale) is mostly zeros -- a block of 64 samples

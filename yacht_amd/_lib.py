@@ -28,6 +28,8 @@ YH_DB_PAIRWISE_ONLY = 8
 YH_DB_NO_DIRECTORY = 16
 YH_RUN_SLOTS = 4
 YH_BATCH_SLOTS = 3
+YH_BATCH_MAX_SAMPLES = 256
+YH_PRESENCE_MAX_COVS = 16
 YH_LOOKUP_AUTO, YH_LOOKUP_STREAM, YH_LOOKUP_INDEXED = 0, 1, 2
 
 _ERR_NAMES = {
@@ -131,6 +133,8 @@ SIGNATURES = {
     "yh_run_batch_finish_range_device": (C.c_int, [_vp, C.c_int, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp]),
     "yh_run_batch_rows_pack_device": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
     "yh_run_batch_rows_unpack_device": (C.c_int, [_vp, C.c_int, _vp, C.c_uint64, _vp, _vp]),
+    "yh_presence_rows_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_int, C.c_double, _vp, C.c_uint32, _vp, C.c_uint32,
+                                          _vp, _vp, _vp]),
     "yh_run_batch_words_packed_len": (C.c_uint64, [C.c_uint64]),
     "yh_run_batch_words_pack_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64]),
     "yh_run_batch_words_unpack_device": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint64, _vp, _vp]),

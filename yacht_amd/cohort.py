@@ -1,0 +1,341 @@
+"""`yacht run` over a cohort: several samples against one trained database in one process.
+
+The database is built once (hypothesis_recovery_src.get_reference_db).  Samples go to the device in blocks of up to
+YH_BATCH_MAX_SAMPLES: one yh_run_batch_device per block, its compact rows (yh_run_batch_rows_pack/_unpack_device; the
+dense rows when the row count exceeds the capacity) and the presence test of those rows on the device
+(yh_presence_rows_device).  The acceptance threshold, confidence and alt. mutation rate depend on n alone: one yh_hyp_test
+over n = 0..max reference size gives their table, gathered on the host by n_cov.  While block j is on the device the host
+assembles block j - 1's tables (the single path's own helpers: coverage_frame, trim_results), host threads parse block
+j + 1, and a pool of --num_threads processes writes the tables.
+
+Output: results/<stem>/ per sample with overlap (what a single-sample run of that file writes into results/),
+results/cohort_samples.tsv and results/cohort_presence.tsv.  Every input is checked before any device work; the
+per-sample intermediate files of the single path (multisearch CSV, list files) are not written.  Every sample is parsed
+in that check (exactly one sketch of the database's k-mer size, its scale); only its size, mean abundance and scale are
+kept, and the sketches are parsed again block by block, so host memory holds a few blocks of samples, not the cohort.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import multiprocessing
+import os
+import time
+import zipfile
+from concurrent.futures import ProcessPoolExecutor, ThreadPoolExecutor
+from pathlib import Path
+from typing import Dict, List
+
+import numpy as np
+import pandas as pd
+
+from . import _lib
+from . import hypothesis_recovery_src as hr
+from . import run_YACHT as ry
+from . import utils
+from .utils import logger
+
+BLOCK = _lib.YH_BATCH_MAX_SAMPLES  # samples per yh_run_batch_device
+MAX_COVS = _lib.YH_PRESENCE_MAX_COVS  # coverages per yh_presence_rows_device (more coverages take more launches)
+SAMPLE_COLUMNS = ["stem", "path", "n_hashes", "mean_abundance", "n_overlapping", "status"]
+PRESENCE_COLUMNS = ["sample", "min_coverage", "organism_name", "num_matches", "acceptance_threshold_with_coverage", "p_vals"]
+
+
+def sample_stem(path: str) -> str:
+    """The sample's name as hypothesis_recovery derives it: the basename without .sig.zip."""
+    return os.path.basename(path).replace(".sig.zip", "")
+
+
+def _check_one(path: str, ksize: int):
+    """(n_hashes, mean_abundance, scaled) of the sample's one sketch of this k-mer size, or the single path's error."""
+    try:
+        mh = utils.load_signature_with_ksize(path, ksize).minhash
+    except ValueError:
+        return None, ValueError(ry.MSG_NOT_ONE_SKETCH.format(path, ksize, len(path)))
+    return (len(mh), mh.mean_abundance, mh.scaled), None
+
+
+def _load_mins(path: str, ksize: int) -> np.ndarray:
+    return np.ascontiguousarray(hr._sample_mins(utils.load_signature_with_ksize(path, ksize)), dtype=np.uint64)
+
+
+def check_inputs(args, files: List[str]) -> dict:
+    """Every check of the single path, for every file, before any device work and before anything is written: the
+    config, the output location, the coverages, the manifest, distinct sample stems, and per file the archive's manifest,
+    exactly one sketch of the database's k-mer size and its scale.  Returns what the run needs; of every sample only
+    meta[i] = (n_hashes, mean_abundance, scaled)."""
+    json_file_path = str(Path(args.json).absolute())
+    paths = [str(Path(f).absolute()) for f in files]
+    outdir = str(Path(args.outdir).absolute())
+    utils.check_file_existence(json_file_path, ry.MSG_NO_CONFIG.format(json_file_path))
+    with open(json_file_path) as f:
+        config = json.load(f)
+    if not os.access(outdir, os.W_OK):
+        raise PermissionError(f"Cannot write to the location: {outdir}.")
+    for x in args.min_coverage_list:
+        if not (0 <= x <= 1):
+            raise ValueError(ry.MSG_BAD_COVERAGE.format(x))
+    utils.check_file_existence(config["manifest_file_path"], ry.MSG_NO_MANIFEST.format(config["manifest_file_path"]))
+    seen: Dict[str, str] = {}
+    for p in paths:
+        stem = sample_stem(p)
+        if stem in seen:
+            raise ValueError(f"Two sample files share the name {stem!r} (results/{stem}/): {seen[stem]} and {p}")
+        seen[stem] = p
+    for p in paths:
+        with zipfile.ZipFile(p, "r") as z:
+            if "SOURMASH-MANIFEST.csv" not in z.namelist():
+                raise FileNotFoundError(ry.MSG_ZIP_WITHOUT_MANIFEST.format(p))
+    ksize, scale = config["ksize"], config["scale"]
+    with ThreadPoolExecutor(max(1, min(int(args.num_threads), len(paths)))) as ex:
+        parsed = list(ex.map(lambda p: _check_one(p, ksize), paths))
+    meta = []
+    for p, (m, err) in zip(paths, parsed):
+        if err is not None:
+            raise err
+        if m[2] != scale:
+            raise ValueError(f"{ry.MSG_SCALE_MISMATCH} Sample: {p}")
+        meta.append(m)
+    return dict(config=config, paths=paths, outdir=outdir, meta=meta)
+
+
+def _write_one(folder: str, results, covs, has_raw: bool, keep_raw: bool, show_all: bool) -> None:
+    os.makedirs(folder, exist_ok=True)
+    ry.write_sample_results(results, covs, has_raw, folder, keep_raw, show_all)
+
+
+class _Device:
+    """The device side of a cohort run: the block's buffers and the calls of one block."""
+
+    def __init__(self, db, covs, ksize: int, ani_thresh: float, thr_table: np.ndarray, cap: int = 0):
+        """cap: compact rows a block may have before it takes the dense rows (0: BLOCK * N, at most 2^20; grows after a
+        block that exceeded it)."""
+        import torch
+
+        self.torch = torch
+        self.db = db
+        self.dev = torch.device(f"cuda:{db.info()['device_id']}")
+        self.covs = np.ascontiguousarray(covs, dtype=np.float64)
+        self.ksize, self.ani = int(ksize), float(ani_thresh)
+        self.thr = torch.from_numpy(np.ascontiguousarray(thr_table, dtype=np.float64)).to(self.dev)
+        self.n_max = int(thr_table.size - 1)
+        N = db.n_refs
+        self.counts = torch.zeros((3, BLOCK, max(N, 1)), dtype=torch.int32, device=self.dev)
+        self.n_rows = torch.zeros(2, dtype=torch.int32, device=self.dev)
+        self.n_rows_host = torch.zeros(2, dtype=torch.int32).pin_memory()
+        self._alloc(int(cap) if cap > 0 else min(BLOCK * max(N, 1), 1 << 20))
+        self.ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+
+    def _alloc(self, cap: int) -> None:
+        t = self.torch
+        self.cap = int(cap)
+        self.vals = t.zeros((self.cap, 3), dtype=t.int32, device=self.dev)
+        self.rows = t.zeros((self.cap, 5), dtype=t.int32, device=self.dev)
+        self.out = self._out(self.cap)
+
+    def _out(self, cap: int):
+        t = self.torch
+        nc = self.covs.size
+        return (t.empty((nc, cap), dtype=t.float64, device=self.dev), t.empty((nc, cap), dtype=t.uint8, device=self.dev),
+                t.empty((nc, cap), dtype=t.int32, device=self.dev))
+
+    def presence(self, rows, d_n_rows: int, cap: int, out) -> None:
+        """yh_presence_rows_device over the rows, MAX_COVS coverages per launch; out = (p_val, present, n_cov) [n_covs][cap]."""
+        from . import _lib
+
+        lib = _lib.load()
+        for c0 in range(0, self.covs.size, MAX_COVS):
+            cv = self.covs[c0:c0 + MAX_COVS]
+            _lib.check(lib.yh_presence_rows_device(self.db._h, C.c_void_p(rows.data_ptr()), C.c_void_p(d_n_rows), cap, self.ksize,
+                                                   self.ani, cv.ctypes.data_as(C.c_void_p), int(cv.size),
+                                                   C.c_void_p(self.thr.data_ptr()), self.n_max,
+                                                   C.c_void_p(out[0][c0].data_ptr()), C.c_void_p(out[1][c0].data_ptr()),
+                                                   C.c_void_p(out[2][c0].data_ptr())))
+
+    def launch(self, mins: List[np.ndarray]) -> int:
+        """Queue one block: upload, batch counts, compact rows, presence test, row count to the host.  No host sync.
+        Events on the caller's (legacy default) stream, which the handle's blocking stream orders against, split the
+        block's device time into upload, counts + compact rows, and the presence kernel."""
+        t = self.torch
+        ev = self.ev
+        ev[0].record()
+        b = len(mins)
+        offs = np.zeros(b + 1, dtype=np.int64)
+        offs[1:] = np.cumsum([m.size for m in mins])
+        cat = np.concatenate(mins).view(np.int64) if offs[-1] else np.zeros(1, np.int64)
+        self.d_samples = t.from_numpy(cat).pin_memory().to(self.dev, non_blocking=True)
+        self.d_offs = t.from_numpy(offs).pin_memory().to(self.dev, non_blocking=True)
+        ev[1].record()
+        c = self.counts
+        self.db.run_batch_device(self.d_samples.data_ptr(), self.d_offs.data_ptr(), b, int(offs[-1]), c[0].data_ptr(),
+                                 c[1].data_ptr(), c[2].data_ptr())
+        self.db.run_batch_rows_pack_device(c[0].data_ptr(), c[1].data_ptr(), c[2].data_ptr(), self.vals.data_ptr(), self.cap,
+                                           self.n_rows[0].data_ptr())
+        self.db.run_batch_rows_unpack_device(self.vals.data_ptr(), self.cap, self.rows.data_ptr(), self.n_rows[1].data_ptr())
+        ev[2].record()
+        self.presence(self.rows, self.n_rows[1].data_ptr(), self.cap, self.out)
+        ev[3].record()
+        self.n_rows_host.copy_(self.n_rows, non_blocking=True)
+        return b
+
+    def collect(self, b: int, timer: Dict[str, float]):
+        """Wait for the block; its rows and the presence results on the host (dense rows when the capacity was short)."""
+        t = self.torch
+        t0 = time.perf_counter()
+        self.db.synchronize()
+        t.cuda.synchronize(self.dev)
+        timer["device_wait"] += time.perf_counter() - t0
+        ev = self.ev
+        timer["gpu_h2d"] += ev[0].elapsed_time(ev[1]) / 1e3
+        timer["gpu_counts"] += ev[1].elapsed_time(ev[2]) / 1e3
+        timer["gpu_presence"] += ev[2].elapsed_time(ev[3]) / 1e3
+        k = int(self.n_rows_host[0])
+        rows, out = self.rows, self.out
+        if k > self.cap:  # more entries than the compact buffers hold: the block's rows from its dense counts
+            ev[0].record()
+            ov = self.counts[0, :b]
+            idx = t.nonzero(ov.t() > 0)  # (reference, sample) order, as the compact rows
+            ref, smp = idx[:, 0], idx[:, 1]
+            rows = t.stack([smp, ref, ov[smp, ref], self.counts[1, smp, ref], self.counts[2, smp, ref]], dim=1).to(t.int32).contiguous()
+            k = int(rows.shape[0])
+            d_k = t.tensor([k], dtype=t.int32, device=self.dev)
+            out = self._out(k)
+            ev[1].record()
+            self.presence(rows, d_k.data_ptr(), k, out)
+            ev[2].record()
+            t0 = time.perf_counter()
+            t.cuda.synchronize(self.dev)
+            timer["device_wait"] += time.perf_counter() - t0
+            timer["gpu_counts"] += ev[0].elapsed_time(ev[1]) / 1e3
+            timer["gpu_presence"] += ev[1].elapsed_time(ev[2]) / 1e3
+            timer["dense_fallback_blocks"] += 1
+            self._alloc(int(k * 1.25) + 1)  # (the next blocks: compact rows again)
+        t0 = time.perf_counter()
+        got = (rows[:k].cpu().numpy().view(np.uint32), out[0][:, :k].cpu().numpy(), out[1][:, :k].cpu().numpy(),
+               out[2][:, :k].cpu().numpy().view(np.uint32))
+        timer["d2h"] += time.perf_counter() - t0
+        return got
+
+
+def main(args, files: List[str]) -> dict:
+    """The cohort form of `yacht run` (run_YACHT.main with two or more --sample_file).  Returns seconds per phase:
+    check (every input, samples parsed once), db (database build), table (the per-n threshold table), device_setup (torch
+    and the device buffers), parse_wait (the loop waiting for a block's sketches), device_wait (the loop waiting for a
+    block's device work), gpu_h2d / gpu_counts / gpu_presence (device time of the uploads, the batch counts + compact rows,
+    the presence kernel), d2h, assemble, writes (what the write pool had left after the last block), cohort_files (the two
+    cohort tables), total."""
+    timer = {k: 0.0 for k in ("check", "db", "table", "device_setup", "parse_wait", "device_wait", "gpu_h2d", "gpu_counts",
+                              "gpu_presence", "d2h", "assemble", "writes", "cohort_files", "dense_fallback_blocks", "total")}
+    t_all = time.perf_counter()
+    t0 = time.perf_counter()
+    plan = check_inputs(args, files)
+    timer["check"] = time.perf_counter() - t0
+    config, paths, meta = plan["config"], plan["paths"], plan["meta"]
+    genome_dir, ksize, ani_thresh = config["intermediate_files_dir"], config["ksize"], config["ani_thresh"]
+    significance = args.significance
+    covs, has_raw = ry.coverage_plan(args.min_coverage_list)
+    user_covs = covs if has_raw else covs[1:]
+    results_folder = os.path.join(plan["outdir"], "results")
+    os.makedirs(results_folder, exist_ok=True)
+    manifest = pd.read_csv(config["manifest_file_path"], sep="\t", header=0)
+    names = manifest["organism_name"].to_numpy()
+    dup_names = bool(manifest["organism_name"].duplicated().any())
+    ry.decompress_legacy_db(genome_dir, args.num_threads)
+
+    t0 = time.perf_counter()
+    db = hr.get_reference_db(manifest, genome_dir, ksize, args.num_threads)
+    timer["db"] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    n_max = int(np.max(db.sizes)) if db.n_refs else 0
+    tab = hr.hyp_test_native(np.arange(n_max + 1), np.zeros(n_max + 1, dtype=np.int64), ksize, significance, ani_thresh, 1.0)
+    t_thr, t_conf, t_alt = tab[5], tab[6], tab[7]
+    timer["table"] = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    dev = _Device(db, covs, ksize, ani_thresh, t_thr)
+    timer["device_setup"] = time.perf_counter() - t0
+
+    blocks = [list(range(i, min(i + BLOCK, len(paths)))) for i in range(0, len(paths), BLOCK)]
+    summary, presence = [], []
+    ctx = multiprocessing.get_context("spawn")  # (the parent holds the GPU: no fork)
+    pool = ProcessPoolExecutor(max_workers=max(1, int(args.num_threads)), mp_context=ctx)
+    futures = []
+    parse_pool = ThreadPoolExecutor(max(1, int(args.num_threads)))
+
+    def parse(block):
+        return [parse_pool.submit(_load_mins, paths[i], ksize) for i in block]
+
+    def assemble(block, mins, got):
+        rows, pv, pres, ncov = got
+        t0 = time.perf_counter()
+        smp = rows[:, 0]
+        order = np.argsort(smp, kind="stable")  # per sample, references ascending (the rows are in (reference, sample) order)
+        bounds = np.searchsorted(smp[order], np.arange(len(block) + 1))
+        for s, i in enumerate(block):
+            sel = order[bounds[s]:bounds[s + 1]]
+            n_hashes, mean_abundance, scaled = meta[i]
+            stem = sample_stem(paths[i])
+            summary.append((stem, paths[i], n_hashes, mean_abundance, int(sel.size), "ok" if sel.size else "no_overlap"))
+            if not sel.size:
+                continue
+            refs = rows[sel, 1].astype(np.int64)
+            e = rows[sel, 3].astype(np.int64)
+            m = rows[sel, 4].astype(np.int64)
+            cols = None
+            if dup_names:  # get_exclusive_hashes selects by NAME: a reference without overlap may share a name with one that has it
+                selected = np.isin(names, names[refs])
+                if int(selected.sum()) != refs.size:
+                    ex_e, ex_m = db.exclusive(selected, mins[s])
+                    refs = np.flatnonzero(selected)
+                    e, m = ex_e[refs].astype(np.int64), ex_m[refs].astype(np.int64)
+                    test = hr.hyp_test_native if os.environ.get("YACHT_HYP_NATIVE") == "1" else hr.hyp_test_batch
+                    cols = [test(e, m, ksize, significance, ani_thresh, cov) for cov in covs]
+            if cols is None:
+                cols = []
+                for c in range(len(covs)):
+                    nc = ncov[c, sel].astype(np.int64)
+                    cols.append((pres[c, sel].astype(bool), pv[c, sel], e, nc, m, t_thr[nc], t_conf[nc], t_alt[nc]))
+            sub = manifest.iloc[refs].reset_index(drop=True)
+            ry.add_sample_columns(sub, mean_abundance, n_hashes, scaled)
+            frames = ry.trim_results([hr.coverage_frame(sub, col, cov) for col, cov in zip(cols, covs)])
+            for cov, df in zip(user_covs, frames if has_raw else frames[1:]):
+                hit = df[df["in_sample_est"] == True]  # noqa: E712
+                if len(hit):
+                    presence.append(pd.DataFrame({"sample": stem, "min_coverage": cov, "organism_name": hit["organism_name"].to_numpy(),
+                                                  "num_matches": hit["num_matches"].to_numpy(),
+                                                  "acceptance_threshold_with_coverage": hit["acceptance_threshold_with_coverage"].to_numpy(),
+                                                  "p_vals": hit["p_vals"].to_numpy()}, columns=PRESENCE_COLUMNS))
+            futures.append(pool.submit(_write_one, os.path.join(results_folder, stem), frames, covs, has_raw, args.keep_raw,
+                                       args.show_all))
+        timer["assemble"] += time.perf_counter() - t0
+
+    try:
+        logger.info(f"Running {len(paths)} samples in {len(blocks)} block(s) of up to {BLOCK}.")
+        pending = None
+        parsing = parse(blocks[0]) if blocks else []
+        for j, block in enumerate(blocks):
+            t0 = time.perf_counter()
+            mins = [f.result() for f in parsing]
+            timer["parse_wait"] += time.perf_counter() - t0
+            parsing = parse(blocks[j + 1]) if j + 1 < len(blocks) else []
+            b = dev.launch(mins)
+            if pending is not None:
+                assemble(*pending)  # (block j - 1 on the host while block j is on the device and block j + 1 is parsed)
+            pending = (block, mins, dev.collect(b, timer))
+        if pending is not None:
+            assemble(*pending)
+        t0 = time.perf_counter()
+        for f in futures:
+            f.result()
+        timer["writes"] = time.perf_counter() - t0  # (the part of the writes not hidden behind the device and the assembly)
+    finally:
+        parse_pool.shutdown(wait=True)
+        pool.shutdown(wait=True)
+        hr.release_reference_dbs()
+    t0 = time.perf_counter()
+    pd.DataFrame(summary, columns=SAMPLE_COLUMNS).to_csv(os.path.join(results_folder, "cohort_samples.tsv"), sep="\t", index=False)
+    (pd.concat(presence, ignore_index=True) if presence else pd.DataFrame(columns=PRESENCE_COLUMNS)).to_csv(
+        os.path.join(results_folder, "cohort_presence.tsv"), sep="\t", index=False)
+    timer["cohort_files"] = time.perf_counter() - t0
+    timer["total"] = time.perf_counter() - t_all
+    logger.info(f"Saved results of {len(paths)} samples to {results_folder}.")
+    return timer

@@ -1313,6 +1313,28 @@ int yh_run_batch_rows_unpack_device(yh_db* db, int slot, const uint32_t* d_vals,
     return yh_q_batch_rows_unpack(db, slot, d_vals, cap_rows, d_rows, d_n_rows);
 }
 
+int yh_q_presence_rows(yh_db* db, const yh_batch_row* d_rows, const u32* d_n_rows, u64 cap_rows, int ksize, double ani_thresh,
+                       const double* min_coverage, u32 n_covs, const double* d_thr, u32 n_max, double* d_p_val, u8* d_present,
+                       u32* d_n_cov);  // yh_presence.hip
+int yh_presence_rows_device(yh_db* db, const yh_batch_row* d_rows, const uint32_t* d_n_rows, uint64_t cap_rows, int ksize,
+                            double ani_thresh, const double* min_coverage, uint32_t n_covs, const double* d_thr, uint32_t n_max,
+                            double* d_p_val, uint8_t* d_present, uint32_t* d_n_cov) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (!d_n_rows || !min_coverage || (cap_rows && (!d_rows || !d_thr || !d_p_val || !d_present || !d_n_cov))) {
+        yh_set_error("null pointer");
+        return YH_ERR_INVALID_ARG;
+    }
+    if (n_covs < 1 || n_covs > YH_PRESENCE_MAX_COVS) { yh_set_error("n_covs must be 1..%d", YH_PRESENCE_MAX_COVS); return YH_ERR_INVALID_ARG; }
+    if (ksize < 1 || !(ani_thresh >= 0.0 && ani_thresh <= 1.0)) { yh_set_error("ksize >= 1 and ani_thresh in [0, 1]"); return YH_ERR_INVALID_ARG; }
+    for (uint32_t c = 0; c < n_covs; ++c)
+        if (!(min_coverage[c] >= 0.0 && min_coverage[c] <= 1.0)) { yh_set_error("min_coverage in [0, 1]"); return YH_ERR_INVALID_ARG; }
+    if (cap_rows > (1ull << 40) / n_covs) { yh_set_error("cap_rows out of range"); return YH_ERR_INVALID_ARG; }
+    YH_TRY(db_select(db));
+    fin_join(db);  // (rows the rows pack / unpack wrote on the finish stream)
+    return yh_q_presence_rows(db, d_rows, d_n_rows, cap_rows, ksize, ani_thresh, min_coverage, n_covs, d_thr, n_max, d_p_val,
+                              d_present, d_n_cov);
+}
+
 uint64_t yh_run_batch_words_packed_len(uint64_t cap_words) { return yh_batch_words_packed_len(cap_words); }
 static bool batch_planes_ok(const yh_db* db, uint32_t n_planes) {
     if (n_planes >= 1 && n_planes <= YH_BATCH_PLANES(YH_BATCH_MAX_SAMPLES) && (u64)n_planes * db->n_refs < 0xffffffffull) return true;

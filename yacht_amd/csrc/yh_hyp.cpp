@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/yacht_hip.h"
+#include "yh_binom.h"
 
 void yh_set_error(const char* fmt, ...);
 
@@ -33,84 +34,23 @@ namespace {
 // The point probability is evaluated in long double (x87 80-bit on the hosts this runs on): its logarithm reaches
 // ~-700 before the result underflows, and a double there carries an absolute error of ~5e-13 -- the size of the
 // disagreement between this file and scipy on p-values around 1e-250 before the change (both were that far from the
-// exact value, on opposite sides).
+// exact value, on opposite sides).  The algorithm itself is yh_binom.h's (the device's presence kernel runs it too).
 typedef long double ld;
 
-// log(n!) - log(sqrt(2 pi n) (n/e)^n) for integer n >= 1 (0 for n = 0: never used as a factor)
-ld stirlerr(ld n) {
+const ld* stirlerr_small() {
     static const std::vector<ld> small = [] {
         std::vector<ld> t(16, 0.0L);
-        ld fact = 1.0L;
-        for (int i = 1; i <= 15; ++i) {
-            fact *= (ld)i;  // exact up to 15!
-            t[i] = logl(fact) - ((ld)i + 0.5L) * logl((ld)i) + (ld)i - 0.918938533204672741780329736406L;
-        }
+        yh_binom::stirlerr_table(t.data());
         return t;
     }();
-    if (n <= 15.0L) return small[(int)n];
-    const ld S0 = 1.0L / 12.0L, S1 = 1.0L / 360.0L, S2 = 1.0L / 1260.0L, S3 = 1.0L / 1680.0L, S4 = 1.0L / 1188.0L,
-             S5 = 691.0L / 360360.0L;
-    const ld nn = n * n;
-    if (n > 500) return (S0 - (S1 - S2 / nn) / nn) / n;
-    if (n > 80) return (S0 - (S1 - (S2 - S3 / nn) / nn) / nn) / n;
-    return (S0 - (S1 - (S2 - (S3 - (S4 - S5 / nn) / nn) / nn) / nn) / nn) / n;
+    return small.data();
 }
 
-// x log(x / np) + np - x without cancellation near x = np
-ld bd0(ld x, ld np) {
-    if (fabsl(x - np) < 0.1L * (x + np)) {
-        ld v = (x - np) / (x + np);
-        ld s = (x - np) * v;
-        ld ej = 2 * x * v;
-        v = v * v;
-        for (int j = 1; j < 1000; ++j) {
-            ej *= v;
-            const ld s1 = s + ej / ((j << 1) + 1);
-            if (s1 == s) return s1;
-            s = s1;
-        }
-        return s;
-    }
-    return x * logl(x / np) + np - x;
-}
-
-// log P[Bin(n, p) = x], 0 <= x <= n, q = 1 - p
-ld log_pmf(double xd, double nd, double pd, double qd) {
-    const ld x = xd, n = nd, p = pd, q = qd;
-    if (p <= 0.0L) return x == 0 ? 0.0L : -INFINITY;
-    if (q <= 0.0L) return x == n ? 0.0L : -INFINITY;
-    if (x == 0) return n * (p < 0.5L ? log1pl(-p) : logl(q));  // (whichever of p, q is the small, exactly known one)
-    if (x == n) return n * (q < 0.5L ? log1pl(-q) : logl(p));
-    const ld lc = stirlerr(n) - stirlerr(x) - stirlerr(n - x) - bd0(x, n * p) - bd0(n - x, n * q);
-    const ld lf = 1.837877066409345483560659472811L + logl(x) + log1pl(-x / n);
-    return lc - 0.5L * lf;
-}
+ld log_pmf(double x, double n, double p, double q) { return yh_binom::log_pmf<ld>(x, n, p, q, stirlerr_small()); }
 
 // P[Bin(n, p) <= k]; q = 1 - p is passed in: the caller knows which of the two is exact
 double binom_cdf(double k, double n, double p, double q) {
-    if (k < 0) return 0.0;
-    if (k >= n) return 1.0;
-    if (p <= 0.0) return 1.0;
-    if (q <= 0.0) return 0.0;  // (k < n)
-    if ((k + 1.0) <= (n + 1.0) * p) {  // k below the mode: the lower tail, terms falling from i = k down
-        const ld l0 = log_pmf(k, n, p, q);
-        ld t = 1.0L, s = 1.0L;
-        for (double i = k; i > 0; i -= 1.0) {
-            t *= ((ld)i * q) / ((ld)(n - i + 1.0) * p);
-            s += t;
-            if (t < s * 1e-22L) break;
-        }
-        return (double)expl(l0 + logl(s));
-    }
-    // k + 1 at or above the mode: the upper tail, terms falling from i = k + 1 up
-    const ld l0 = log_pmf(k + 1.0, n, p, q);
-    ld t = 1.0L, s = 1.0L;
-    for (double i = k + 1.0; i < n; i += 1.0) {
-        t *= ((ld)(n - i) * p) / ((ld)(i + 1.0) * q);
-        s += t;
-        if (t < s * 1e-22L) break;
-    }
-    return (double)(1.0L - expl(l0 + logl(s)));
+    return yh_binom::binom_cdf<ld>(k, n, p, q, stirlerr_small(), 1e-22L);
 }
 
 // smallest k in [0, n] with cdf(k) >= prob

@@ -309,8 +309,15 @@ def hypothesis_recovery(manifest: pd.DataFrame, sample_info_set, path_to_genome_
             test = hyp_test_native if os.environ.get("YACHT_HYP_NATIVE") == "1" else hyp_test_batch
             cols = test(n_excl, n_match, ksize, significance, ani_thresh, min_coverage)
         with phases.phase("assemble_frames"):
-            results = pd.DataFrame({name: col for name, col in zip(GIVEN_COLUMNS, cols)}, columns=GIVEN_COLUMNS)
-            results["in_sample_est"] = results["in_sample_est"].astype(bool)
-            manifest["min_coverage"] = min_coverage
-            out.append(pd.concat([manifest, results], axis=1))
+            out.append(coverage_frame(manifest, cols, min_coverage))
     return out
+
+
+def coverage_frame(manifest: pd.DataFrame, cols, min_coverage: float) -> pd.DataFrame:
+    """One coverage's result table: the sub-manifest (its min_coverage column set to this coverage) joined with the eight
+    hypothesis-test columns `cols` (hyp_test_batch's order).  hypothesis_recovery and the cohort driver both build their
+    tables here."""
+    results = pd.DataFrame({name: col for name, col in zip(GIVEN_COLUMNS, cols)}, columns=GIVEN_COLUMNS)
+    results["in_sample_est"] = results["in_sample_est"].astype(bool)
+    manifest["min_coverage"] = min_coverage
+    return pd.concat([manifest, results], axis=1)

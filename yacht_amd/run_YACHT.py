@@ -35,7 +35,11 @@ RAW_RENAMES = {
 # (flag, keyword arguments of add_argument): the reference's argument set (run_YACHT.py:24-72)
 ARGUMENTS = (
     ("--json", dict(type=str, required=True, help="Config json written by `yacht train`.")),
-    ("--sample_file", dict(required=True, help="Metagenomic sample in .sig.zip format")),
+    ("--sample_file", dict(required=True, nargs="+",
+                           help="Metagenomic sample in .sig.zip format.  Two or more files run as one cohort against the database "
+                                "built once: results/<stem>/ per sample plus results/cohort_samples.tsv and "
+                                "results/cohort_presence.tsv; the per-sample intermediate files (multisearch CSV, list files) "
+                                "are not written then.")),
     ("--significance", dict(type=float, default=0.99, help="Minimum probability of individual true negative.")),
     ("--num_threads", dict(type=int, default=16, help="Host threads for file handling.")),
     ("--keep_raw", dict(action="store_true", help="Keep raw results in output file.")),
@@ -86,9 +90,52 @@ def write_tables(tables, results_folder: str) -> None:
     xlsx.write_xlsx(os.path.join(results_folder, "result.xlsx"), tables)
 
 
+def add_sample_columns(manifest: pd.DataFrame, mean_abundance, n_hashes: int, scaled: int) -> None:
+    """The sample's columns of the result tables (run_YACHT.py:159-162 of the reference; the mean abundance goes into
+    "num_exclusive_kmers_in_sample_sketch" on purpose, see the module docstring)."""
+    manifest["num_exclusive_kmers_in_sample_sketch"] = mean_abundance
+    manifest["num_total_kmers_in_sample_sketch"] = utils.get_num_kmers(mean_abundance, n_hashes, scaled, scale=False)
+    manifest["sample_scale_factor"] = scaled
+    manifest["min_coverage"] = 1.0
+
+
+def trim_results(results):
+    """The columns a result table keeps, under the names the reference writes (run_YACHT.py:215-220)."""
+    return [r[[c for c in r.columns if c not in ("md5sum", "sample_scale_factor")]]
+            .rename(columns={"genome_scale_factor": "scale_factor"}) for r in results]
+
+
+def write_sample_results(results, covs, has_raw: bool, results_folder: str, keep_raw: bool, show_all: bool) -> None:
+    """result_all.txt, result.xlsx and sheets/*.tsv of one sample from its trimmed tables (one per coverage of `covs`)."""
+    user_results = results if has_raw else results[1:]
+    user_covs = covs if has_raw else covs[1:]
+    pd.concat(user_results, ignore_index=True).to_csv(os.path.join(results_folder, "result_all.txt"), sep="\t", index=False)
+    tables = []
+    if keep_raw:
+        tables.append(("raw_result", results[0].rename(columns=RAW_RENAMES)))
+    for cov, df in zip(user_covs, user_results):
+        tables.append((f"min_coverage{cov}", df if show_all else df[df["in_sample_est"] == True]))  # noqa: E712
+    write_tables(tables, results_folder)
+
+
+def decompress_legacy_db(genome_dir: str, num_threads: int) -> None:
+    """Databases trained by old versions list *.sig.gz: decompress them once (run_YACHT.py:184-189)."""
+    listed = glob.glob(f"{genome_dir}/training_sig_files.*")
+    if listed:
+        df = pd.read_csv(listed[0], sep="\t", header=None)
+        if len(df) and "sig.gz" in df[0].values[0]:
+            pd.DataFrame([x.replace("sig.gz", "sig") for x in df[0]]).to_csv(listed[0], header=False, index=False)
+            utils.decompress_all_sig_files(glob.glob(f"{genome_dir}/signatures/*.sig.gz"), num_threads)
+
+
 def main(args) -> None:
+    files = [args.sample_file] if isinstance(args.sample_file, str) else list(args.sample_file)
+    if len(files) > 1:
+        from . import cohort
+
+        return cohort.main(args, files)
     json_file_path = str(Path(args.json).absolute())
-    sample_file = str(Path(args.sample_file).absolute())
+    sample_file = str(Path(files[0]).absolute())
     outdir = str(Path(args.outdir).absolute())
     results_folder = os.path.join(outdir, "results")
     os.makedirs(results_folder, exist_ok=True)
@@ -122,43 +169,25 @@ def main(args) -> None:
         # (the reference parses the file a second time here, run_YACHT.py:150-152 -> utils.py:89-110; same tuple)
         info = (sample_file, sample_sig.name, sample_sig.md5sum(), sample_sig.minhash.mean_abundance,
                 len(sample_sig.minhash), sample_sig.minhash.scaled)
-    manifest["num_exclusive_kmers_in_sample_sketch"] = info[3]
-    manifest["num_total_kmers_in_sample_sketch"] = utils.get_num_kmers(info[3], info[4], info[5], scale=False)
-    manifest["sample_scale_factor"] = info[5]
-    manifest["min_coverage"] = 1.0
+    add_sample_columns(manifest, info[3], info[4], info[5])
     if scale != info[5]:
         raise ValueError(MSG_SCALE_MISMATCH)
 
     covs, has_raw = coverage_plan(args.min_coverage_list)
 
-    # databases trained by old versions list *.sig.gz: decompress them once (run_YACHT.py:184-189)
-    listed = glob.glob(f"{genome_dir}/training_sig_files.*")
-    if listed:
-        df = pd.read_csv(listed[0], sep="\t", header=None)
-        if len(df) and "sig.gz" in df[0].values[0]:
-            pd.DataFrame([x.replace("sig.gz", "sig") for x in df[0]]).to_csv(listed[0], header=False, index=False)
-            utils.decompress_all_sig_files(glob.glob(f"{genome_dir}/signatures/*.sig.gz"), args.num_threads)
+    decompress_legacy_db(genome_dir, args.num_threads)
 
     logger.info("Computing hypothesis recovery.")
     with phases.phase("hypothesis_recovery"):
         results = hr.hypothesis_recovery(manifest, (sample_file, sample_sig), genome_dir, covs, scale, ksize,
                                          args.significance, ani_thresh, args.num_threads)
     hr.release_reference_dbs()
-    results = [r[[c for c in r.columns if c not in ("md5sum", "sample_scale_factor")]]
-               .rename(columns={"genome_scale_factor": "scale_factor"}) for r in results]
+    results = trim_results(results)
 
     logger.info(f"Saving results to {results_folder}.")
     _t_write = phases.phase("write_results")
     _t_write.__enter__()
-    user_results = results if has_raw else results[1:]
-    user_covs = covs if has_raw else covs[1:]
-    pd.concat(user_results, ignore_index=True).to_csv(os.path.join(results_folder, "result_all.txt"), sep="\t", index=False)
-    tables = []
-    if args.keep_raw:
-        tables.append(("raw_result", results[0].rename(columns=RAW_RENAMES)))
-    for cov, df in zip(user_covs, user_results):
-        tables.append((f"min_coverage{cov}", df if args.show_all else df[df["in_sample_est"] == True]))  # noqa: E712
-    write_tables(tables, results_folder)
+    write_sample_results(results, covs, has_raw, results_folder, args.keep_raw, args.show_all)
     _t_write.__exit__(None, None, None)
 
 
