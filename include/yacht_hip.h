@@ -384,7 +384,8 @@ int yh_run_batch_rows_unpack_device(yh_db* db, int slot, const uint32_t* d_vals,
  * (n_covs <= YH_PRESENCE_MAX_COVS), outputs [n_covs][cap_rows] (index c * cap_rows + k):
  *   d_n_cov[.]   = (uint32_t)((double)n_excl * min_coverage[c])        (yh_hyp_test's n_excl_cov)
  *   d_p_val[.]   = binom.cdf(n_match, n_cov, ani_thresh ** ksize) if n_match <= n_cov else 1   (yh_hyp_test's p_val, in
- *                  double on the device: ~1e-12 relative of the host's long double)
+ *                  double on the device: within 5e-13 relative of the exact value where that is >= 1e-300, 6e-14
+ *                  where it is >= 1e-15, for n_cov up to 3e7; yh_hyp_test's own is within 1e-15)
  *   d_present[.] = n_match >= d_thr[n_cov] && n_match != 0
  * d_thr[0 .. n_max] (device) = the acceptance thresholds by n: one yh_hyp_test over n_excl = 0..n_max, n_match = 0,
  * min_coverage = 1 gives them, and its confidence / alt. mutation rate columns are the host's table of the other two

@@ -46,11 +46,23 @@ const ld* stirlerr_small() {
     return small.data();
 }
 
-ld log_pmf(double x, double n, double p, double q) { return yh_binom::log_pmf<ld>(x, n, p, q, stirlerr_small()); }
+// log P[Bin(n, p) = x] for an exact p
+ld log_pmf(double x, double n, double p) {
+    double q_lo;
+    const double q = yh_binom::one_minus(p, &q_lo);
+    return yh_binom::log_pmf<ld>(x, n, p, q, q_lo, stirlerr_small());
+}
 
-// P[Bin(n, p) <= k]; q = 1 - p is passed in: the caller knows which of the two is exact
-double binom_cdf(double k, double n, double p, double q) {
-    return yh_binom::binom_cdf<ld>(k, n, p, q, stirlerr_small(), 1e-22L);
+// P[Bin(n, p) <= k] for an exact p: 1 - p is formed in long double (exact for p >= 2^-11)
+double binom_cdf(double k, double n, double p) {
+    double q_lo;
+    const double q = yh_binom::one_minus(p, &q_lo);
+    return yh_binom::binom_cdf<ld>(k, n, p, q, q_lo, stirlerr_small(), 1e-22L);
+}
+
+// P[Bin(n, 1 - q) <= k] for an exact q (1 - q only rounded)
+double binom_cdf_q(double k, double n, double q) {
+    return yh_binom::binom_cdf<ld>(k, n, 1.0 - q, q, 0.0, stirlerr_small(), 1e-22L);
 }
 
 // smallest k in [0, n] with cdf(k) >= prob
@@ -58,7 +70,7 @@ double binom_ppf(double prob, double n, double p) {
     if (n <= 0) return 0.0;
     if (!(prob > 0.0)) return -1.0;  // (scipy: a - 1)
     if (prob >= 1.0) return n;
-    const double q = 1.0 - p;
+    const double q = 1.0 - p;  // (the starting guess only)
     // normal approximation of the quantile as the starting point
     double z = 0.0;
     {   // Acklam's rational approximation of the normal quantile (a starting guess only)
@@ -79,10 +91,10 @@ double binom_ppf(double prob, double n, double p) {
     }
     double k = floor(n * p + z * sqrt(n * p * q) + 0.5);
     k = std::min(std::max(k, 0.0), n);
-    if (binom_cdf(k, n, p, q) >= prob) {
-        while (k > 0 && binom_cdf(k - 1.0, n, p, q) >= prob) k -= 1.0;
+    if (binom_cdf(k, n, p) >= prob) {
+        while (k > 0 && binom_cdf(k - 1.0, n, p) >= prob) k -= 1.0;
     } else {
-        do k += 1.0; while (k < n && binom_cdf(k, n, p, q) < prob);
+        do k += 1.0; while (k < n && binom_cdf(k, n, p) < prob);
     }
     return k;
 }
@@ -93,9 +105,9 @@ double betaincinv_int(double n, double t, double y) {
     if (!(a > 0.0) || !(t >= 0.0) || !(y >= 0.0) || !(y <= 1.0)) return NAN;
     if (y == 0.0) return 0.0;
     if (y == 1.0) return 1.0;
-    auto g = [&](double x) { return binom_cdf(t, n, 1.0 - x, x); };
+    auto g = [&](double x) { return binom_cdf_q(t, n, x); };
     // derivative: x^(a-1) (1-x)^(b-1) / B(a, b) = n * P[Bin(n - 1, x) = a - 1]
-    auto dg = [&](double x) { return n * (double)expl(log_pmf(a - 1.0, n - 1.0, x, 1.0 - x)); };
+    auto dg = [&](double x) { return n * (double)expl(log_pmf(a - 1.0, n - 1.0, x)); };
     double lo = 0.0, hi = 1.0;
     double x = a / (a + t + 1.0);  // the mean of Beta(a, b)
     x = std::min(std::max(x, 1e-300), 1.0 - 1e-16);
@@ -158,7 +170,7 @@ extern "C" int yh_hyp_test(uint64_t n, const uint32_t* n_excl, const uint32_t* n
             const double nn = (double)uniq[i];
             PerN r;
             r.thr = binom_ppf(q_prob, nn, p);
-            r.conf = 1.0 - binom_cdf(r.thr, nn, p, 1.0 - p);
+            r.conf = 1.0 - binom_cdf(r.thr, nn, p);
             const double x = betaincinv_int(nn, r.thr, significance);
             const double mut = 1.0 - pow(1.0 - x, 1.0 / (double)ksize);
             r.alt = std::isnan(mut) ? -1.0 : mut;
@@ -172,7 +184,7 @@ extern "C" int yh_hyp_test(uint64_t n, const uint32_t* n_excl, const uint32_t* n
             confidence[i] = r.conf;
             alt_mut_rate[i] = r.alt;
             const double m = (double)n_match[i];
-            p_val[i] = (n_match[i] <= ncov[i]) ? binom_cdf(m, (double)ncov[i], p, 1.0 - p) : 1.0;
+            p_val[i] = (n_match[i] <= ncov[i]) ? binom_cdf(m, (double)ncov[i], p) : 1.0;
             in_sample_est[i] = (m >= r.thr && n_match[i] != 0) ? 1 : 0;
         }
     });

@@ -23,7 +23,7 @@ constexpr int PRESENCE_BLOCK = 256;
 struct PresenceArgs {
     double cov[YH_PRESENCE_MAX_COVS];
     double small[16];  // stirlerr(0..15)
-    double p, q;
+    double p, q, q_lo;  // q + q_lo = 1 - p exactly
     uint32_t n_max;
     uint64_t cap_rows;
 };
@@ -42,7 +42,7 @@ __global__ __launch_bounds__(PRESENCE_BLOCK) void k_presence_rows(PresenceArgs a
         double pv = 1.0;
         u8 pr = 0;
         if (nc <= a.n_max) {
-            if (r.n_match <= nc) pv = yh_binom::binom_cdf<double>((double)r.n_match, (double)nc, a.p, a.q, a.small, 1e-22);
+            if (r.n_match <= nc) pv = yh_binom::binom_cdf<double>((double)r.n_match, (double)nc, a.p, a.q, a.q_lo, a.small, 1e-22);
             pr = ((double)r.n_match >= thr[nc] && r.n_match != 0) ? 1 : 0;
         } else {
             pv = NAN;  // outside the caller's table: no decision (the caller sizes the table by the largest reference)
@@ -65,7 +65,7 @@ extern "C" int yh_q_presence_rows(yh_db* db, const yh_batch_row* d_rows, const u
     yh_binom::stirlerr_table(sl);
     for (int i = 0; i < 16; ++i) a.small[i] = (double)sl[i];
     a.p = pow(ani_thresh, (double)ksize);  // (yh_hyp.cpp's p)
-    a.q = 1.0 - a.p;
+    a.q = yh_binom::one_minus(a.p, &a.q_lo);
     a.n_max = n_max;
     a.cap_rows = cap_rows;
     const u64 want = (cap_rows + PRESENCE_BLOCK - 1) / PRESENCE_BLOCK;
