@@ -294,6 +294,7 @@ int yh_run_device_join(yh_db* db);
  *   yh_run_rows_device, yh_run_device_join,                  | yes (they only complete pending        | yes
  *     yh_db_synchronize, yh_db_get_timing, yh_db_get_info    |   pipelined stages)                    |
  *   yh_pairwise, yh_index_stats, yh_db_nshared_device        | yes                                   | yes
+ *   yh_abund / yh_abund_device                               | yes (no step state is read or written) | yes
  *   yh_db_set_stream                                         | yes (drains the old stream first)      | yes
  *   (*) the CURRENT context = the one named by the last yh_run_local*_device / yh_run_finish*_device call (0 at start).
  * Every query entry point first completes the pending stages of pipelined steps (yh_run_device_join) by itself.          */
@@ -396,6 +397,31 @@ int yh_run_batch_rows_unpack_device(yh_db* db, int slot, const uint32_t* d_vals,
 int yh_presence_rows_device(yh_db* db, const yh_batch_row* d_rows, const uint32_t* d_n_rows, uint64_t cap_rows, int ksize,
                             double ani_thresh, const double* min_coverage, uint32_t n_covs, const double* d_thr, uint32_t n_max,
                             double* d_p_val, uint8_t* d_present, uint32_t* d_n_cov);
+
+/* ---- per-reference DEPTH of a sample with per-hash abundances (additive in ABI 8) ------------------------------------------
+ * For a sample S (strictly ascending) whose hash h was seen abund(h) times, and every reference j in [0, N):
+ *   w_overlap[j] = sum of abund(h) over h in S ∩ R_j
+ *   w_match[j]   = sum of abund(h) over the h in S whose ONLY holder in the database is j
+ *   med_match[j] = median of abund(h) over that same set (even count: mean of the two middle values, so always x.0 or x.5;
+ *                  empty set: 0.0); med_match / d_med_match may be NULL: the sums alone, without the sort the median needs
+ * The set behind w_match and med_match is the one yh_run counts as n_match: n_match[j] counts the hashes of R_j that are in
+ * the sample and in no other reference of the run subset (overlap > 0); a sample hash held by j and k gives BOTH overlap, so
+ * both are in the subset, and a sample hash is exclusive to j exactly when j is its only holder in the database (the same for
+ * any superset of the subset).  With all abundances 1 the sums therefore equal yh_run's overlap and n_match.  The pass needs
+ * no subset bits: it reads no step context and no batch slot (interleaving table above: yes / yes), completes pending
+ * pipelined stages first like every query entry, and is enqueued on the handle's stream; the device form does not sync the
+ * host, the host form is synchronous and validates the sample's ordering.  n_sample == 0 gives zeroed outputs.  The sums are
+ * integer adds (bit-reproducible).
+ * YH_ERR_UNSUPPORTED: a handle without the directory or the index (YH_DB_NO_DIRECTORY, YH_DB_NO_INDEX,
+ * YH_DB_PAIRWISE_ONLY), or with ghosts registered (yh_db_set_ghosts: exclusivity is then not local to the handle).
+ * Hash-range shards: the two sums ADD over the ranks; the median does not (it needs the ranks' hit lists merged).  Nothing
+ * is built for shards.
+ * (No reference counterpart: the reference reports only the mean abundance of the whole sample.  Nearest elsewhere:
+ * `sourmash gather`'s average_abund / median_abund.)                                                                      */
+int yh_abund_device(yh_db* db, const uint64_t* d_sample, const uint32_t* d_abund, uint64_t n_sample,
+                    uint64_t* d_w_overlap, uint64_t* d_w_match, double* d_med_match);   /* [N] each */
+int yh_abund(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_t n_sample,
+             uint64_t* w_overlap, uint64_t* w_match, double* med_match);
 
 /* ---- the subset words of a block in compact form (ABI 5) ----------------------------------------------------------------
  * Between the two halves of a batched hash-range run every rank needs the OR of all ranks' subset words.  The dense row

@@ -39,6 +39,7 @@ BLOCK = _lib.YH_BATCH_MAX_SAMPLES  # samples per yh_run_batch_device
 MAX_COVS = _lib.YH_PRESENCE_MAX_COVS  # coverages per yh_presence_rows_device (more coverages take more launches)
 SAMPLE_COLUMNS = ["stem", "path", "n_hashes", "mean_abundance", "n_overlapping", "status"]
 PRESENCE_COLUMNS = ["sample", "min_coverage", "organism_name", "num_matches", "acceptance_threshold_with_coverage", "p_vals"]
+PRESENCE_ABUNDANCE_COLUMNS = ["abund_median_exclusive", "relative_abundance"]  # behind them with --abundance
 
 
 def sample_stem(path: str) -> str:
@@ -57,6 +58,15 @@ def _check_one(path: str, ksize: int):
 
 def _load_mins(path: str, ksize: int) -> np.ndarray:
     return np.ascontiguousarray(hr._sample_mins(utils.load_signature_with_ksize(path, ksize)), dtype=np.uint64)
+
+
+def _load_mins_abund(path: str, ksize: int):
+    """(hashes, their abundances as uint32) of a sample (--abundance)."""
+    from . import abundance
+    from .engine import check_abundances
+
+    sig = utils.load_signature_with_ksize(path, ksize)
+    return check_abundances(hr._sample_mins(sig), abundance.sample_abundances(sig, path))
 
 
 def check_inputs(args, files: List[str]) -> dict:
@@ -95,21 +105,29 @@ def check_inputs(args, files: List[str]) -> dict:
             raise err
         if m[2] != scale:
             raise ValueError(f"{ry.MSG_SCALE_MISMATCH} Sample: {p}")
+        if getattr(args, "abundance", False) and m[1] is None:
+            from . import abundance
+
+            raise ValueError(abundance.MSG_NO_ABUNDANCE.format(p))
         meta.append(m)
     return dict(config=config, paths=paths, outdir=outdir, meta=meta)
 
 
-def _write_one(folder: str, results, covs, has_raw: bool, keep_raw: bool, show_all: bool) -> None:
+def _write_one(folder: str, results, covs, has_raw: bool, keep_raw: bool, show_all: bool, profile: bool = False) -> None:
     os.makedirs(folder, exist_ok=True)
     ry.write_sample_results(results, covs, has_raw, folder, keep_raw, show_all)
+    if profile:
+        from . import abundance
+
+        abundance.write_profile(results if has_raw else results[1:], covs if has_raw else covs[1:], folder)
 
 
 class _Device:
     """The device side of a cohort run: the block's buffers and the calls of one block."""
 
-    def __init__(self, db, covs, ksize: int, ani_thresh: float, thr_table: np.ndarray, cap: int = 0):
+    def __init__(self, db, covs, ksize: int, ani_thresh: float, thr_table: np.ndarray, cap: int = 0, abund_samples: int = 0):
         """cap: compact rows a block may have before it takes the dense rows (0: BLOCK * N, at most 2^20; grows after a
-        block that exceeded it)."""
+        block that exceeded it).  abund_samples (--abundance): samples of the largest block; 0 = no abundance pass."""
         import torch
 
         self.torch = torch
@@ -125,6 +143,13 @@ class _Device:
         self.n_rows_host = torch.zeros(2, dtype=torch.int32).pin_memory()
         self._alloc(int(cap) if cap > 0 else min(BLOCK * max(N, 1), 1 << 20))
         self.ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        self.abund = None
+        if abund_samples > 0:  # [samples][N] sums and medians of a block (yh_abund_device, one call per sample)
+            shape = (int(abund_samples), max(N, 1))
+            self.abund = (torch.zeros(shape, dtype=torch.int64, device=self.dev), torch.zeros(shape, dtype=torch.int64, device=self.dev),
+                          torch.zeros(shape, dtype=torch.float64, device=self.dev))
+            self.abund_rows = None
+            self.ev_abund = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
 
     def _alloc(self, cap: int) -> None:
         t = self.torch
@@ -152,7 +177,24 @@ class _Device:
                                                    C.c_void_p(out[0][c0].data_ptr()), C.c_void_p(out[1][c0].data_ptr()),
                                                    C.c_void_p(out[2][c0].data_ptr())))
 
-    def launch(self, mins: List[np.ndarray]) -> int:
+    def abundance_pass(self, offs: np.ndarray, b: int) -> None:
+        """The block's abundance pass: yh_abund_device once per sample on its slice of the uploaded block, then the three
+        values of every compact row (sample, reference) gathered on the device."""
+        w_ov, w_m, med = self.abund
+        for s in range(b):
+            self.db.abundance_device(self.d_samples.data_ptr() + 8 * int(offs[s]), self.d_abund.data_ptr() + 4 * int(offs[s]),
+                                     int(offs[s + 1] - offs[s]), w_ov[s].data_ptr(), w_m[s].data_ptr(), med[s].data_ptr())
+        self.abund_rows = self.gather_abundance(self.rows, b)
+
+    def gather_abundance(self, rows, b: int):
+        """(w_overlap, w_match, med_match) at the rows' (sample, reference); rows behind the block's count are clamped
+        into range and never read on the host."""
+        w_ov, w_m, med = self.abund
+        smp = rows[:, 0].long().clamp_(0, max(b - 1, 0))
+        ref = rows[:, 1].long().clamp_(0, w_ov.shape[1] - 1)
+        return w_ov[smp, ref], w_m[smp, ref], med[smp, ref]
+
+    def launch(self, mins: List[np.ndarray], abunds=None) -> int:
         """Queue one block: upload, batch counts, compact rows, presence test, row count to the host.  No host sync.
         Events on the caller's (legacy default) stream, which the handle's blocking stream orders against, split the
         block's device time into upload, counts + compact rows, and the presence kernel."""
@@ -175,6 +217,12 @@ class _Device:
         ev[2].record()
         self.presence(self.rows, self.n_rows[1].data_ptr(), self.cap, self.out)
         ev[3].record()
+        if abunds is not None:
+            cat_ab = np.concatenate(abunds).view(np.int32) if offs[-1] else np.zeros(1, np.int32)
+            self.d_abund = t.from_numpy(cat_ab).pin_memory().to(self.dev, non_blocking=True)
+            self.ev_abund[0].record()
+            self.abundance_pass(offs, b)
+            self.ev_abund[1].record()
         self.n_rows_host.copy_(self.n_rows, non_blocking=True)
         return b
 
@@ -189,8 +237,11 @@ class _Device:
         timer["gpu_h2d"] += ev[0].elapsed_time(ev[1]) / 1e3
         timer["gpu_counts"] += ev[1].elapsed_time(ev[2]) / 1e3
         timer["gpu_presence"] += ev[2].elapsed_time(ev[3]) / 1e3
+        if self.abund is not None:
+            timer["gpu_abund"] += self.ev_abund[0].elapsed_time(self.ev_abund[1]) / 1e3
         k = int(self.n_rows_host[0])
         rows, out = self.rows, self.out
+        abund_rows = self.abund_rows if self.abund is not None else None
         if k > self.cap:  # more entries than the compact buffers hold: the block's rows from its dense counts
             ev[0].record()
             ov = self.counts[0, :b]
@@ -203,6 +254,8 @@ class _Device:
             ev[1].record()
             self.presence(rows, d_k.data_ptr(), k, out)
             ev[2].record()
+            if self.abund is not None:
+                abund_rows = self.gather_abundance(rows, b)
             t0 = time.perf_counter()
             t.cuda.synchronize(self.dev)
             timer["device_wait"] += time.perf_counter() - t0
@@ -213,6 +266,9 @@ class _Device:
         t0 = time.perf_counter()
         got = (rows[:k].cpu().numpy().view(np.uint32), out[0][:, :k].cpu().numpy(), out[1][:, :k].cpu().numpy(),
                out[2][:, :k].cpu().numpy().view(np.uint32))
+        if abund_rows is not None:
+            got += ((abund_rows[0][:k].cpu().numpy().view(np.uint64), abund_rows[1][:k].cpu().numpy().view(np.uint64),
+                     abund_rows[2][:k].cpu().numpy()),)
         timer["d2h"] += time.perf_counter() - t0
         return got
 
@@ -222,10 +278,11 @@ def main(args, files: List[str]) -> dict:
     check (every input, samples parsed once), db (database build), table (the per-n threshold table), device_setup (torch
     and the device buffers), parse_wait (the loop waiting for a block's sketches), device_wait (the loop waiting for a
     block's device work), gpu_h2d / gpu_counts / gpu_presence (device time of the uploads, the batch counts + compact rows,
-    the presence kernel), d2h, assemble, writes (what the write pool had left after the last block), cohort_files (the two
+    the presence kernel), gpu_abund (with --abundance: the block's yh_abund_device calls and the gather of their values at the
+    compact rows), d2h, assemble, writes (what the write pool had left after the last block), cohort_files (the two
     cohort tables), total."""
     timer = {k: 0.0 for k in ("check", "db", "table", "device_setup", "parse_wait", "device_wait", "gpu_h2d", "gpu_counts",
-                              "gpu_presence", "d2h", "assemble", "writes", "cohort_files", "dense_fallback_blocks", "total")}
+                              "gpu_presence", "gpu_abund", "d2h", "assemble", "writes", "cohort_files", "dense_fallback_blocks", "total")}
     t_all = time.perf_counter()
     t0 = time.perf_counter()
     plan = check_inputs(args, files)
@@ -251,21 +308,25 @@ def main(args, files: List[str]) -> dict:
     t_thr, t_conf, t_alt = tab[5], tab[6], tab[7]
     timer["table"] = time.perf_counter() - t0
     t0 = time.perf_counter()
-    dev = _Device(db, covs, ksize, ani_thresh, t_thr)
+    want_abundance = bool(getattr(args, "abundance", False))
+    if want_abundance:
+        from . import abundance
+    dev = _Device(db, covs, ksize, ani_thresh, t_thr, abund_samples=min(BLOCK, len(paths)) if want_abundance else 0)
     timer["device_setup"] = time.perf_counter() - t0
 
     blocks = [list(range(i, min(i + BLOCK, len(paths)))) for i in range(0, len(paths), BLOCK)]
     summary, presence = [], []
+    presence_columns = PRESENCE_COLUMNS + (PRESENCE_ABUNDANCE_COLUMNS if want_abundance else [])
     ctx = multiprocessing.get_context("spawn")  # (the parent holds the GPU: no fork)
     pool = ProcessPoolExecutor(max_workers=max(1, int(args.num_threads)), mp_context=ctx)
     futures = []
     parse_pool = ThreadPoolExecutor(max(1, int(args.num_threads)))
 
     def parse(block):
-        return [parse_pool.submit(_load_mins, paths[i], ksize) for i in block]
+        return [parse_pool.submit(_load_mins_abund if want_abundance else _load_mins, paths[i], ksize) for i in block]
 
-    def assemble(block, mins, got):
-        rows, pv, pres, ncov = got
+    def assemble(block, mins, got, abunds=None):
+        rows, pv, pres, ncov = got[:4]
         t0 = time.perf_counter()
         smp = rows[:, 0]
         order = np.argsort(smp, kind="stable")  # per sample, references ascending (the rows are in (reference, sample) order)
@@ -281,10 +342,18 @@ def main(args, files: List[str]) -> dict:
             e = rows[sel, 3].astype(np.int64)
             m = rows[sel, 4].astype(np.int64)
             cols = None
+            if want_abundance:  # the device's three values and the overlap count of the sample's rows
+                depth = [got[4][0][sel], got[4][1][sel], got[4][2][sel], rows[sel, 2]]
             if dup_names:  # get_exclusive_hashes selects by NAME: a reference without overlap may share a name with one that has it
                 selected = np.isin(names, names[refs])
                 if int(selected.sum()) != refs.size:
                     ex_e, ex_m = db.exclusive(selected, mins[s])
+                    if want_abundance:  # references pulled in by name have no overlap: sums 0, means and median NaN
+                        at = np.searchsorted(np.flatnonzero(selected), refs)
+                        wide = [np.zeros(int(selected.sum()), dtype=a.dtype) for a in depth]
+                        for w, a in zip(wide, depth):
+                            w[at] = a
+                        depth = wide
                     refs = np.flatnonzero(selected)
                     e, m = ex_e[refs].astype(np.int64), ex_m[refs].astype(np.int64)
                     test = hr.hyp_test_native if os.environ.get("YACHT_HYP_NATIVE") == "1" else hr.hyp_test_batch
@@ -296,16 +365,23 @@ def main(args, files: List[str]) -> dict:
                     cols.append((pres[c, sel].astype(bool), pv[c, sel], e, nc, m, t_thr[nc], t_conf[nc], t_alt[nc]))
             sub = manifest.iloc[refs].reset_index(drop=True)
             ry.add_sample_columns(sub, mean_abundance, n_hashes, scaled)
-            frames = ry.trim_results([hr.coverage_frame(sub, col, cov) for col, cov in zip(cols, covs)])
+            frames = [hr.coverage_frame(sub, col, cov) for col, cov in zip(cols, covs)]
+            if want_abundance:
+                total = int(abunds[s].sum(dtype=np.uint64))
+                frames = [abundance.append_columns(f, *depth, total) for f in frames]
+            frames = ry.trim_results(frames)
             for cov, df in zip(user_covs, frames if has_raw else frames[1:]):
                 hit = df[df["in_sample_est"] == True]  # noqa: E712
                 if len(hit):
-                    presence.append(pd.DataFrame({"sample": stem, "min_coverage": cov, "organism_name": hit["organism_name"].to_numpy(),
-                                                  "num_matches": hit["num_matches"].to_numpy(),
-                                                  "acceptance_threshold_with_coverage": hit["acceptance_threshold_with_coverage"].to_numpy(),
-                                                  "p_vals": hit["p_vals"].to_numpy()}, columns=PRESENCE_COLUMNS))
+                    part = {"sample": stem, "min_coverage": cov, "organism_name": hit["organism_name"].to_numpy(),
+                            "num_matches": hit["num_matches"].to_numpy(),
+                            "acceptance_threshold_with_coverage": hit["acceptance_threshold_with_coverage"].to_numpy(),
+                            "p_vals": hit["p_vals"].to_numpy()}
+                    for c in PRESENCE_ABUNDANCE_COLUMNS if want_abundance else ():
+                        part[c] = hit[c].to_numpy()
+                    presence.append(pd.DataFrame(part, columns=presence_columns))
             futures.append(pool.submit(_write_one, os.path.join(results_folder, stem), frames, covs, has_raw, args.keep_raw,
-                                       args.show_all))
+                                       args.show_all, want_abundance))
         timer["assemble"] += time.perf_counter() - t0
 
     try:
@@ -315,12 +391,15 @@ def main(args, files: List[str]) -> dict:
         for j, block in enumerate(blocks):
             t0 = time.perf_counter()
             mins = [f.result() for f in parsing]
+            abunds = None
+            if want_abundance:
+                mins, abunds = [x[0] for x in mins], [x[1] for x in mins]
             timer["parse_wait"] += time.perf_counter() - t0
             parsing = parse(blocks[j + 1]) if j + 1 < len(blocks) else []
-            b = dev.launch(mins)
+            b = dev.launch(mins, abunds)
             if pending is not None:
                 assemble(*pending)  # (block j - 1 on the host while block j is on the device and block j + 1 is parsed)
-            pending = (block, mins, dev.collect(b, timer))
+            pending = (block, mins, dev.collect(b, timer), abunds)
         if pending is not None:
             assemble(*pending)
         t0 = time.perf_counter()
@@ -333,7 +412,7 @@ def main(args, files: List[str]) -> dict:
         hr.release_reference_dbs()
     t0 = time.perf_counter()
     pd.DataFrame(summary, columns=SAMPLE_COLUMNS).to_csv(os.path.join(results_folder, "cohort_samples.tsv"), sep="\t", index=False)
-    (pd.concat(presence, ignore_index=True) if presence else pd.DataFrame(columns=PRESENCE_COLUMNS)).to_csv(
+    (pd.concat(presence, ignore_index=True) if presence else pd.DataFrame(columns=presence_columns)).to_csv(
         os.path.join(results_folder, "cohort_presence.tsv"), sep="\t", index=False)
     timer["cohort_files"] = time.perf_counter() - t0
     timer["total"] = time.perf_counter() - t_all

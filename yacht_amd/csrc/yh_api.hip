@@ -1,5 +1,6 @@
 // yh_api.hip — the extern "C" boundary of libyacht_hip.so (declared in include/yacht_hip.h).
 #include "yh_common.h"
+#include "yh_abund.h"
 #include "yh_sort.h"
 #include "yh_pack.h"
 
@@ -1126,6 +1127,62 @@ int yh_run(yh_db* db, const uint64_t* sample, uint64_t n_sample, uint32_t* overl
         yh_set_error("the sample sketch is not strictly ascending");
         rc = YH_ERR_UNSORTED;
     }
+    return rc;
+}
+
+// ---- abundance-weighted sums and the median depth per reference (yh_abund.hip) ----------------------------------
+static int abund_supported(yh_db* db) {
+    if (!db->has_dir || !db->has_index || (db->n_shared && (!db->d_po || !db->d_pr))) {
+        yh_set_error("yh_abund needs the directory of the distinct hashes and the index "
+                     "(not YH_DB_NO_DIRECTORY, YH_DB_NO_INDEX or YH_DB_PAIRWISE_ONLY)");
+        return YH_ERR_UNSUPPORTED;
+    }
+    if (db->n_ghost) {
+        yh_set_error("yh_abund on a handle with ghosts: the only holder of a hash on this rank need not be its only holder");
+        return YH_ERR_UNSUPPORTED;
+    }
+    return YH_OK;
+}
+
+int yh_abund_device(yh_db* db, const uint64_t* d_sample, const uint32_t* d_abund, uint64_t n_sample, uint64_t* d_w_overlap,
+                    uint64_t* d_w_match, double* d_med_match) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (!d_w_overlap || !d_w_match || (n_sample && (!d_sample || !d_abund))) { yh_set_error("null device pointer"); return YH_ERR_INVALID_ARG; }
+    YH_TRY(abund_supported(db));
+    YH_TRY(db_select(db));
+    YH_TRY(pipe_join(db));  // (no step context, batch slot or work list is read or written: nothing else to note)
+    return yh_q_abund(db, (const u64*)d_sample, d_abund, n_sample, (u64*)d_w_overlap, (u64*)d_w_match, d_med_match);
+}
+
+int yh_abund(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_t n_sample, uint64_t* w_overlap, uint64_t* w_match,
+             double* med_match) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    const u64 N = db->n_refs;
+    if ((N && (!w_overlap || !w_match)) || (n_sample && (!sample || !abund))) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+    YH_TRY(abund_supported(db));
+    YH_TRY(db_select(db));
+    YH_TRY(upload_sample(db, sample, n_sample));
+    if (N == 0) return YH_OK;
+    u32* d_a = nullptr;
+    u64* d_out = nullptr;
+    int rc = YH_OK;
+    do {
+        if (yh_tmalloc(db, (void**)&d_a, std::max<u64>(n_sample, 4) * sizeof(u32)) != hipSuccess ||
+            yh_tmalloc(db, (void**)&d_out, 3 * N * sizeof(u64)) != hipSuccess) { yh_set_error("device allocation failed"); rc = YH_ERR_OOM; break; }
+        if (n_sample && hipMemcpyAsync(d_a, abund, n_sample * sizeof(u32), hipMemcpyHostToDevice, db->stream) != hipSuccess) {
+            yh_set_error("abundance upload failed"); rc = YH_ERR_HIP; break;
+        }
+        double* const d_med = med_match ? (double*)(d_out + 2 * N) : nullptr;
+        if ((rc = yh_abund_device(db, (const uint64_t*)db->d_sample_tmp, d_a, n_sample, (uint64_t*)d_out, (uint64_t*)(d_out + N), d_med)) != YH_OK) break;
+        const bool down_ok = hipMemcpyAsync(w_overlap, d_out, N * sizeof(u64), hipMemcpyDeviceToHost, db->stream) == hipSuccess &&
+                             hipMemcpyAsync(w_match, d_out + N, N * sizeof(u64), hipMemcpyDeviceToHost, db->stream) == hipSuccess &&
+                             (!med_match || hipMemcpyAsync(med_match, d_med, N * sizeof(double), hipMemcpyDeviceToHost, db->stream) == hipSuccess);
+        if (!down_ok || hipStreamSynchronize(db->stream) != hipSuccess) {
+            yh_set_error("abundance download failed: %s", hipGetErrorString(hipGetLastError()));
+            rc = YH_ERR_HIP;
+        }
+    } while (0);
+    yh_tfree(db, d_a); yh_tfree(db, d_out);
     return rc;
 }
 

@@ -77,6 +77,20 @@ def _ptr(a: Optional[np.ndarray]) -> C.c_void_p:
     return C.c_void_p(0 if a is None else a.ctypes.data)
 
 
+def check_abundances(sample, abund) -> Tuple[np.ndarray, np.ndarray]:
+    """(sample as uint64, abund as uint32) for RefDB.abundance, or ValueError: one abundance per sample hash, each in
+    [0, 2**32 - 1].  Host only: no library call."""
+    sample = _as_u64(sample)
+    abund = np.asarray(abund)
+    if abund.ndim != 1 or abund.size != sample.size:
+        raise ValueError(f"abund must hold one abundance per sample hash: {abund.size} abundances for {sample.size} hashes")
+    if abund.size and abund.dtype.kind not in "iu":
+        raise ValueError(f"abundances must be integers, not {abund.dtype}")
+    if abund.size and (int(abund.max()) > 0xFFFFFFFF or int(abund.min()) < 0):
+        raise ValueError("abundances must lie in [0, 2**32 - 1]: the device sums them as 32-bit counts")
+    return sample, np.ascontiguousarray(abund, dtype=np.uint32)
+
+
 class RefDB:
     """Reference sketches in HBM: delta stream, bucket table + presence filter, shared-hash inverted index."""
 
@@ -225,6 +239,22 @@ class RefDB:
         m = np.zeros(self.n_refs, dtype=np.uint32)
         _lib.check(self._lib.yh_run(self._h, _ptr(sample), sample.size, _ptr(ov), _ptr(e), _ptr(m)))
         return ov, e, m
+
+    def abundance(self, sample, abund) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Depth of the sample over every reference (yh_abund): w_overlap[j] = sum of abund over the sample hashes in R_j,
+        w_match[j] = the same over the sample hashes whose only holder is j (the set run_counts counts as n_match), both
+        uint64, and med_match[j] = the median abundance over that set (float64; 0.0 where it is empty)."""
+        sample, abund = check_abundances(sample, abund)
+        w_ov = np.zeros(self.n_refs, dtype=np.uint64)
+        w_m = np.zeros(self.n_refs, dtype=np.uint64)
+        med = np.zeros(self.n_refs, dtype=np.float64)
+        _lib.check(self._lib.yh_abund(self._h, _ptr(sample), _ptr(abund), sample.size, _ptr(w_ov), _ptr(w_m), _ptr(med)))
+        return w_ov, w_m, med
+
+    def abundance_device(self, d_sample: int, d_abund: int, n_sample: int, d_w_overlap: int, d_w_match: int, d_med: int = 0) -> None:
+        """yh_abund_device: uint64 sample and uint32 abundances in, uint64 [N] sums and (d_med != 0) float64 [N] medians out."""
+        _lib.check(self._lib.yh_abund_device(self._h, C.c_void_p(d_sample), C.c_void_p(d_abund), n_sample, C.c_void_p(d_w_overlap),
+                                             C.c_void_p(d_w_match), C.c_void_p(d_med)))
 
     # sharded run (dist.ShardedRefDB): the step in two halves around the exchange of the subset bits
     def set_ghosts(self, ghost_begin: int, n_ghost: int, d_ghost_src: int) -> None:

@@ -281,9 +281,10 @@ def single_hyp_test(exclusive_hashes_info_org: Tuple[int, int], ksize: int, sign
 
 def hypothesis_recovery(manifest: pd.DataFrame, sample_info_set, path_to_genome_temp_dir: str,
                         min_coverage_list: List[float], scale: int, ksize: int, significance: float = 0.99,
-                        ani_thresh: float = 0.95, num_threads: int = 16):
+                        ani_thresh: float = 0.95, num_threads: int = 16, abundances=None):
     """One DataFrame per min_coverage: the sub-manifest of overlapping organisms joined with the
-    eight hypothesis-test columns (reference :309-417)."""
+    eight hypothesis-test columns (reference :309-417).  abundances (`yacht run --abundance`): the sample's per-hash
+    abundances, in the order of its hashes; the tables then carry abundance.ABUNDANCE_COLUMNS behind those eight."""
     sample_file, sample_sig = sample_info_set
     sample_dir = os.path.dirname(sample_file)
     sample_name = os.path.basename(sample_file).replace(".sig.zip", "")
@@ -297,6 +298,15 @@ def hypothesis_recovery(manifest: pd.DataFrame, sample_info_set, path_to_genome_
     names = get_organisms_with_nonzero_overlap(manifest, sample_file, scale, ksize, num_threads,
                                                path_to_genome_temp_dir, path_to_sample_temp_dir,
                                                parsed_sample=sample_sig if hasattr(sample_sig, "minhash") else None)
+    depth = None
+    if abundances is not None:  # one more call on the resident database, for the rows get_exclusive_hashes selects
+        from . import abundance
+
+        with phases.phase("abundance"):
+            rows = np.flatnonzero(manifest["organism_name"].isin(names).to_numpy())
+            w_overlap, w_match, med_match = _LAST_RUN["db"].abundance(_LAST_RUN["mins"], abundances)
+            depth = (w_overlap[rows], w_match[rows], med_match[rows], _LAST_RUN["overlap"][rows],
+                     int(np.asarray(abundances, dtype=np.uint64).sum()))
     with phases.phase("exclusive_hashes_bookkeeping"):
         info, manifest = get_exclusive_hashes(manifest, names, sample_sig, ksize, path_to_genome_temp_dir)
         n_excl = np.array([x[0] for x in info], dtype=np.int64)
@@ -309,7 +319,8 @@ def hypothesis_recovery(manifest: pd.DataFrame, sample_info_set, path_to_genome_
             test = hyp_test_native if os.environ.get("YACHT_HYP_NATIVE") == "1" else hyp_test_batch
             cols = test(n_excl, n_match, ksize, significance, ani_thresh, min_coverage)
         with phases.phase("assemble_frames"):
-            out.append(coverage_frame(manifest, cols, min_coverage))
+            frame = coverage_frame(manifest, cols, min_coverage)
+            out.append(frame if depth is None else abundance.append_columns(frame, *depth))
     return out
 
 

@@ -47,6 +47,10 @@ ARGUMENTS = (
     ("--min_coverage_list", dict(nargs="+", type=float, default=[1, 0.5, 0.1, 0.05, 0.01],
                                  help="Fractions of a genome's unique k-mers assumed covered by the sample, each in [0, 1].")),
     ("--outdir", dict(type=str, default=os.getcwd(), help="Where the 'results' folder is created.")),
+    ("--abundance", dict(action="store_true",
+                         help="Also estimate how much of each organism the sample holds: the depth (sum, mean, median of the "
+                              "sample's per-hash abundances) over the k-mers exclusive to each genome, as extra columns of "
+                              "every table and as results/abundance_profile.tsv.  Needs a sample sketched with abundances.")),
 )
 
 # messages the reference raises with (callers and its tests match on them)
@@ -172,6 +176,13 @@ def main(args) -> None:
     add_sample_columns(manifest, info[3], info[4], info[5])
     if scale != info[5]:
         raise ValueError(MSG_SCALE_MISMATCH)
+    want_abundance = bool(getattr(args, "abundance", False))
+    sample_abund = None
+    if want_abundance:
+        from . import abundance
+
+        with phases.phase("load_abundances"):
+            sample_abund = abundance.sample_abundances(sample_sig, sample_file)
 
     covs, has_raw = coverage_plan(args.min_coverage_list)
 
@@ -180,7 +191,8 @@ def main(args) -> None:
     logger.info("Computing hypothesis recovery.")
     with phases.phase("hypothesis_recovery"):
         results = hr.hypothesis_recovery(manifest, (sample_file, sample_sig), genome_dir, covs, scale, ksize,
-                                         args.significance, ani_thresh, args.num_threads)
+                                         args.significance, ani_thresh, args.num_threads,
+                                         **({"abundances": sample_abund} if want_abundance else {}))
     hr.release_reference_dbs()
     results = trim_results(results)
 
@@ -188,6 +200,8 @@ def main(args) -> None:
     _t_write = phases.phase("write_results")
     _t_write.__enter__()
     write_sample_results(results, covs, has_raw, results_folder, args.keep_raw, args.show_all)
+    if want_abundance:
+        abundance.write_profile(results if has_raw else results[1:], covs if has_raw else covs[1:], results_folder)
     _t_write.__exit__(None, None, None)
 
 
