@@ -295,6 +295,7 @@ int yh_run_device_join(yh_db* db);
  *     yh_db_synchronize, yh_db_get_timing, yh_db_get_info    |   pipelined stages)                    |
  *   yh_pairwise, yh_index_stats, yh_db_nshared_device        | yes                                   | yes
  *   yh_abund / yh_abund_device                               | yes (no step state is read or written) | yes
+ *   yh_explain / yh_explain_device                           | yes (no step state is read or written) | yes
  *   yh_db_set_stream                                         | yes (drains the old stream first)      | yes
  *   (*) the CURRENT context = the one named by the last yh_run_local*_device / yh_run_finish*_device call (0 at start).
  * Every query entry point first completes the pending stages of pipelined steps (yh_run_device_join) by itself.          */
@@ -422,6 +423,32 @@ int yh_abund_device(yh_db* db, const uint64_t* d_sample, const uint32_t* d_abund
                     uint64_t* d_w_overlap, uint64_t* d_w_match, double* d_med_match);   /* [N] each */
 int yh_abund(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_t n_sample,
              uint64_t* w_overlap, uint64_t* w_match, double* med_match);
+
+/* ---- what of a sample a set of references EXPLAINS, per sample hash (additive in ABI 8) --------------------------------------
+ * Every query above reduces over the sample and answers per reference; this one answers per SAMPLE HASH.  Inputs: the sample S
+ * (strictly ascending), optional abundances abund(h) (NULL: every abund(h) = 1), and a member table member[N] of one byte per
+ * reference: bit k of member[j], k in 0..6, says that reference j belongs to call set k (for `yacht run`: the organisms
+ * called present at one min_coverage), so one pass answers up to seven call sets.  Bit 7 must be clear: the host form returns
+ * YH_ERR_INVALID_ARG for a byte that has it, the device form masks it off.  Outputs, for every sample hash h:
+ *   flags[h] = 0                                              if no reference of the database holds h
+ *   flags[h] = 0x80 | OR over ALL holders j of h (member[j])  otherwise
+ * (bit 7: known to the database; bit k: held by at least one reference of call set k -- a shared hash with one holder inside
+ * call set k and others outside it is explained by call set k), and the fixed [8][2] array
+ *   totals[b][0] = #{h in S : flags[h] has bit b set},   totals[b][1] = sum of abund(h) over the same hashes.
+ * flags / d_flags may be NULL: the totals only.  n_sample == 0 or an empty database: zero totals, and no flag is written.
+ * All outputs are integers and do not depend on arrival order.  The pass reads no step context, batch slot or work list
+ * (interleaving table above: yes / yes), completes pending pipelined stages first like every query entry, and is enqueued on
+ * the handle's stream; the device form does not sync the host, the host form is synchronous, validates the sample's
+ * ordering (YH_ERR_UNSORTED), uploads, runs and downloads.
+ * YH_ERR_UNSUPPORTED: a handle without the directory or the index (YH_DB_NO_DIRECTORY, YH_DB_NO_INDEX,
+ * YH_DB_PAIRWISE_ONLY), or with ghosts registered (yh_db_set_ghosts).
+ * Hash-range shards: each hash lives on one rank, so over the ranks the flags OR and the totals ADD.  Nothing is built for
+ * shards.
+ * (No reference counterpart: its MAG_fishing / low_abundance_samples use cases subtract sketches with Python sets.)            */
+int yh_explain_device(yh_db* db, const uint64_t* d_sample, const uint32_t* d_abund /* NULL: all 1 */, uint64_t n_sample,
+                      const uint8_t* d_member /* [N] */, uint8_t* d_flags /* [n_sample] or NULL */, uint64_t* d_totals /* [8][2] */);
+int yh_explain(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_t n_sample,
+               const uint8_t* member, uint8_t* flags, uint64_t* totals);
 
 /* ---- the subset words of a block in compact form (ABI 5) ----------------------------------------------------------------
  * Between the two halves of a batched hash-range run every rank needs the OR of all ranks' subset words.  The dense row

@@ -69,11 +69,27 @@ def _load_mins_abund(path: str, ksize: int):
     return check_abundances(hr._sample_mins(sig), abundance.sample_abundances(sig, path))
 
 
+def _load_for_residual(path: str, ksize: int, want_abundance: bool):
+    """(hashes, their abundances as uint32 or None, the signature) of a sample (--residual): the abundances when the sketch
+    tracks them, which --abundance insists on."""
+    from . import abundance, residual
+    from .engine import check_abundances
+
+    sig = utils.load_signature_with_ksize(path, ksize)
+    mins = np.ascontiguousarray(hr._sample_mins(sig), dtype=np.uint64)
+    ab = abundance.sample_abundances(sig, path) if want_abundance else residual.sample_abundances_or_none(sig)
+    return (mins, None, sig) if ab is None else (*check_abundances(mins, ab), sig)
+
+
 def check_inputs(args, files: List[str]) -> dict:
     """Every check of the single path, for every file, before any device work and before anything is written: the
     config, the output location, the coverages, the manifest, distinct sample stems, and per file the archive's manifest,
     exactly one sketch of the database's k-mer size and its scale.  Returns what the run needs; of every sample only
     meta[i] = (n_hashes, mean_abundance, scaled)."""
+    if getattr(args, "residual", False) or getattr(args, "residual_coverage", None) is not None:
+        from . import residual
+
+        residual.residual_coverage(args)
     json_file_path = str(Path(args.json).absolute())
     paths = [str(Path(f).absolute()) for f in files]
     outdir = str(Path(args.outdir).absolute())
@@ -113,13 +129,18 @@ def check_inputs(args, files: List[str]) -> dict:
     return dict(config=config, paths=paths, outdir=outdir, meta=meta)
 
 
-def _write_one(folder: str, results, covs, has_raw: bool, keep_raw: bool, show_all: bool, profile: bool = False) -> None:
+def _write_one(folder: str, results, covs, has_raw: bool, keep_raw: bool, show_all: bool, profile: bool = False, explained=None) -> None:
     os.makedirs(folder, exist_ok=True)
     ry.write_sample_results(results, covs, has_raw, folder, keep_raw, show_all)
     if profile:
         from . import abundance
 
         abundance.write_profile(results if has_raw else results[1:], covs if has_raw else covs[1:], folder)
+    if explained is not None:  # (sample signature, call sets, flags, totals, residual coverage) of --residual
+        from . import residual
+
+        sig, call_sets, flags, totals, cov = explained
+        residual.write_outputs(folder, sig, covs if has_raw else covs[1:], call_sets, flags, totals, cov)
 
 
 class _Device:
@@ -279,10 +300,11 @@ def main(args, files: List[str]) -> dict:
     and the device buffers), parse_wait (the loop waiting for a block's sketches), device_wait (the loop waiting for a
     block's device work), gpu_h2d / gpu_counts / gpu_presence (device time of the uploads, the batch counts + compact rows,
     the presence kernel), gpu_abund (with --abundance: the block's yh_abund_device calls and the gather of their values at the
-    compact rows), d2h, assemble, writes (what the write pool had left after the last block), cohort_files (the two
+    compact rows), gpu_explain (with --residual: the samples' host-form yh_explain calls, each of which uploads its sample
+    again and waits behind the device work of the next block), d2h, assemble, writes (what the write pool had left after the last block), cohort_files (the two
     cohort tables), total."""
     timer = {k: 0.0 for k in ("check", "db", "table", "device_setup", "parse_wait", "device_wait", "gpu_h2d", "gpu_counts",
-                              "gpu_presence", "gpu_abund", "d2h", "assemble", "writes", "cohort_files", "dense_fallback_blocks", "total")}
+                              "gpu_presence", "gpu_abund", "gpu_explain", "d2h", "assemble", "writes", "cohort_files", "dense_fallback_blocks", "total")}
     t_all = time.perf_counter()
     t0 = time.perf_counter()
     plan = check_inputs(args, files)
@@ -311,6 +333,11 @@ def main(args, files: List[str]) -> dict:
     want_abundance = bool(getattr(args, "abundance", False))
     if want_abundance:
         from . import abundance
+    want_residual = bool(getattr(args, "residual", False))
+    if want_residual:
+        from . import residual
+
+        residual_cov = residual.residual_coverage(args)
     dev = _Device(db, covs, ksize, ani_thresh, t_thr, abund_samples=min(BLOCK, len(paths)) if want_abundance else 0)
     timer["device_setup"] = time.perf_counter() - t0
 
@@ -323,9 +350,11 @@ def main(args, files: List[str]) -> dict:
     parse_pool = ThreadPoolExecutor(max(1, int(args.num_threads)))
 
     def parse(block):
+        if want_residual:
+            return [parse_pool.submit(_load_for_residual, paths[i], ksize, want_abundance) for i in block]
         return [parse_pool.submit(_load_mins_abund if want_abundance else _load_mins, paths[i], ksize) for i in block]
 
-    def assemble(block, mins, got, abunds=None):
+    def assemble(block, mins, got, abunds=None, sigs=None):
         rows, pv, pres, ncov = got[:4]
         t0 = time.perf_counter()
         smp = rows[:, 0]
@@ -335,7 +364,8 @@ def main(args, files: List[str]) -> dict:
             sel = order[bounds[s]:bounds[s + 1]]
             n_hashes, mean_abundance, scaled = meta[i]
             stem = sample_stem(paths[i])
-            summary.append((stem, paths[i], n_hashes, mean_abundance, int(sel.size), "ok" if sel.size else "no_overlap"))
+            summary.append([stem, paths[i], n_hashes, mean_abundance, int(sel.size), "ok" if sel.size else "no_overlap"]
+                           + ([0.0, 0.0] if want_residual else []))  # (no overlap: nothing explained, and no device call)
             if not sel.size:
                 continue
             refs = rows[sel, 1].astype(np.int64)
@@ -370,6 +400,18 @@ def main(args, files: List[str]) -> dict:
                 total = int(abunds[s].sum(dtype=np.uint64))
                 frames = [abundance.append_columns(f, *depth, total) for f in frames]
             frames = ry.trim_results(frames)
+            explained = None
+            if want_residual:  # this sample's final presence calls are known: one host-form call (seven coverages each)
+                call_sets = [refs[df["in_sample_est"].to_numpy().astype(bool)] for df in (frames if has_raw else frames[1:])]
+                t1 = time.perf_counter()
+                flags, totals = residual.explain_call_sets(db, mins[s], abunds[s] if abunds is not None else None, call_sets)
+                timer["gpu_explain"] += time.perf_counter() - t1
+                mh = sigs[s].minhash
+                total = n_hashes if mh.abundances is None else int(np.asarray(mh.abundances, dtype=np.uint64).sum(dtype=np.uint64))
+                row = residual.explained_frame(user_covs, [len(c) for c in call_sets], totals, n_hashes, total)
+                row = row[row["min_coverage"] == residual_cov].iloc[0]
+                summary[-1][-2:] = [float(row["f_hashes_explained"]), float(row["f_abund_explained"])]
+                explained = (sigs[s], call_sets, flags, totals, residual_cov)
             for cov, df in zip(user_covs, frames if has_raw else frames[1:]):
                 hit = df[df["in_sample_est"] == True]  # noqa: E712
                 if len(hit):
@@ -381,7 +423,7 @@ def main(args, files: List[str]) -> dict:
                         part[c] = hit[c].to_numpy()
                     presence.append(pd.DataFrame(part, columns=presence_columns))
             futures.append(pool.submit(_write_one, os.path.join(results_folder, stem), frames, covs, has_raw, args.keep_raw,
-                                       args.show_all, want_abundance))
+                                       args.show_all, want_abundance, explained))
         timer["assemble"] += time.perf_counter() - t0
 
     try:
@@ -391,15 +433,17 @@ def main(args, files: List[str]) -> dict:
         for j, block in enumerate(blocks):
             t0 = time.perf_counter()
             mins = [f.result() for f in parsing]
-            abunds = None
-            if want_abundance:
+            abunds = sigs = None
+            if want_residual:  # (abundances where the sketch tracks them; --abundance has checked that every one does)
+                mins, abunds, sigs = [x[0] for x in mins], [x[1] for x in mins], [x[2] for x in mins]
+            elif want_abundance:
                 mins, abunds = [x[0] for x in mins], [x[1] for x in mins]
             timer["parse_wait"] += time.perf_counter() - t0
             parsing = parse(blocks[j + 1]) if j + 1 < len(blocks) else []
-            b = dev.launch(mins, abunds)
+            b = dev.launch(mins, abunds if want_abundance else None)
             if pending is not None:
                 assemble(*pending)  # (block j - 1 on the host while block j is on the device and block j + 1 is parsed)
-            pending = (block, mins, dev.collect(b, timer), abunds)
+            pending = (block, mins, dev.collect(b, timer), abunds, sigs)
         if pending is not None:
             assemble(*pending)
         t0 = time.perf_counter()
@@ -411,7 +455,7 @@ def main(args, files: List[str]) -> dict:
         pool.shutdown(wait=True)
         hr.release_reference_dbs()
     t0 = time.perf_counter()
-    pd.DataFrame(summary, columns=SAMPLE_COLUMNS).to_csv(os.path.join(results_folder, "cohort_samples.tsv"), sep="\t", index=False)
+    pd.DataFrame(summary, columns=SAMPLE_COLUMNS + (residual.COHORT_COLUMNS if want_residual else [])).to_csv(os.path.join(results_folder, "cohort_samples.tsv"), sep="\t", index=False)
     (pd.concat(presence, ignore_index=True) if presence else pd.DataFrame(columns=presence_columns)).to_csv(
         os.path.join(results_folder, "cohort_presence.tsv"), sep="\t", index=False)
     timer["cohort_files"] = time.perf_counter() - t0

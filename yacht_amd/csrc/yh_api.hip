@@ -1,6 +1,7 @@
 // yh_api.hip — the extern "C" boundary of libyacht_hip.so (declared in include/yacht_hip.h).
 #include "yh_common.h"
 #include "yh_abund.h"
+#include "yh_explain.h"
 #include "yh_sort.h"
 #include "yh_pack.h"
 
@@ -1183,6 +1184,69 @@ int yh_abund(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_t 
         }
     } while (0);
     yh_tfree(db, d_a); yh_tfree(db, d_out);
+    return rc;
+}
+
+// ---- what of a sample the members of up to seven call sets explain, per sample hash (yh_explain.hip) -----------
+static int explain_supported(yh_db* db) {
+    if (!db->has_dir || !db->has_index || (db->n_shared && (!db->d_po || !db->d_pr))) {
+        yh_set_error("yh_explain needs the directory of the distinct hashes and the index "
+                     "(not YH_DB_NO_DIRECTORY, YH_DB_NO_INDEX or YH_DB_PAIRWISE_ONLY)");
+        return YH_ERR_UNSUPPORTED;
+    }
+    if (db->n_ghost) {
+        yh_set_error("yh_explain on a handle with ghosts: a ghost's member byte belongs to the rank that owns the reference");
+        return YH_ERR_UNSUPPORTED;
+    }
+    return YH_OK;
+}
+
+int yh_explain_device(yh_db* db, const uint64_t* d_sample, const uint32_t* d_abund, uint64_t n_sample, const uint8_t* d_member,
+                      uint8_t* d_flags, uint64_t* d_totals) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (!d_totals || (n_sample && !d_sample) || (n_sample && db->n_refs && !d_member)) { yh_set_error("null device pointer"); return YH_ERR_INVALID_ARG; }
+    YH_TRY(explain_supported(db));
+    YH_TRY(db_select(db));
+    YH_TRY(pipe_join(db));  // (no step context, batch slot or work list is read or written: nothing else to note)
+    return yh_q_explain(db, (const u64*)d_sample, d_abund, n_sample, d_member, d_flags, (u64*)d_totals);
+}
+
+int yh_explain(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_t n_sample, const uint8_t* member, uint8_t* flags,
+               uint64_t* totals) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    const u64 N = db->n_refs;
+    if (!totals || (N && !member) || (n_sample && !sample)) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+    for (u64 j = 0; j < N; ++j)
+        if (member[j] & 0x80u) {
+            yh_set_error("member[%llu] has bit 7 set: the call sets are bits 0..6, bit 7 of a flag means \"in the database\"", (u64)j);
+            return YH_ERR_INVALID_ARG;
+        }
+    YH_TRY(explain_supported(db));
+    YH_TRY(db_select(db));
+    YH_TRY(upload_sample(db, sample, n_sample));
+    const bool looks_up = n_sample && N && db->n_distinct;  // (otherwise: zero totals, no flags written)
+    u32* d_a = nullptr;
+    u8* d_bytes = nullptr;  // the totals (128 bytes), the member table, the flags
+    const u64 off_member = 16 * sizeof(u64), off_flags = off_member + ((N + 15) & ~15ull);
+    int rc = YH_OK;
+    do {
+        if ((abund && yh_tmalloc(db, (void**)&d_a, std::max<u64>(n_sample, 4) * sizeof(u32)) != hipSuccess) ||
+            yh_tmalloc(db, (void**)&d_bytes, off_flags + std::max<u64>(n_sample, 16)) != hipSuccess) { yh_set_error("device allocation failed"); rc = YH_ERR_OOM; break; }
+        if ((abund && n_sample && hipMemcpyAsync(d_a, abund, n_sample * sizeof(u32), hipMemcpyHostToDevice, db->stream) != hipSuccess) ||
+            (N && hipMemcpyAsync(d_bytes + off_member, member, N, hipMemcpyHostToDevice, db->stream) != hipSuccess)) {
+            yh_set_error("explain upload failed"); rc = YH_ERR_HIP; break;
+        }
+        u8* const d_flags = flags ? d_bytes + off_flags : nullptr;
+        if ((rc = yh_explain_device(db, (const uint64_t*)db->d_sample_tmp, abund ? d_a : nullptr, n_sample, d_bytes + off_member, d_flags,
+                                    (uint64_t*)d_bytes)) != YH_OK) break;
+        const bool down_ok = hipMemcpyAsync(totals, d_bytes, 16 * sizeof(u64), hipMemcpyDeviceToHost, db->stream) == hipSuccess &&
+                             (!flags || !looks_up || hipMemcpyAsync(flags, d_flags, n_sample, hipMemcpyDeviceToHost, db->stream) == hipSuccess);
+        if (!down_ok || hipStreamSynchronize(db->stream) != hipSuccess) {
+            yh_set_error("explain download failed: %s", hipGetErrorString(hipGetLastError()));
+            rc = YH_ERR_HIP;
+        }
+    } while (0);
+    yh_tfree(db, d_a); yh_tfree(db, d_bytes);
     return rc;
 }
 

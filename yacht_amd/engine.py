@@ -91,6 +91,19 @@ def check_abundances(sample, abund) -> Tuple[np.ndarray, np.ndarray]:
     return sample, np.ascontiguousarray(abund, dtype=np.uint32)
 
 
+def check_member(member, n_refs: int) -> np.ndarray:
+    """The member table of RefDB.explain as uint8 [n_refs], or ValueError: one byte per reference, each in [0, 127] (bits
+    0..6 are the call sets; bit 7 of a flag means "in the database").  Host only: no library call."""
+    member = np.asarray(member)
+    if member.ndim != 1 or member.size != int(n_refs):
+        raise ValueError(f"member must hold one byte per reference: {member.size} bytes for {int(n_refs)} references")
+    if member.size and member.dtype.kind not in "iub":
+        raise ValueError(f"member bytes must be integers, not {member.dtype}")
+    if member.size and (int(member.max()) > 0x7F or int(member.min()) < 0):
+        raise ValueError("member bytes must lie in [0, 127]: bit 7 must be clear, the call sets are bits 0..6")
+    return np.ascontiguousarray(member, dtype=np.uint8)
+
+
 class RefDB:
     """Reference sketches in HBM: delta stream, bucket table + presence filter, shared-hash inverted index."""
 
@@ -255,6 +268,28 @@ class RefDB:
         """yh_abund_device: uint64 sample and uint32 abundances in, uint64 [N] sums and (d_med != 0) float64 [N] medians out."""
         _lib.check(self._lib.yh_abund_device(self._h, C.c_void_p(d_sample), C.c_void_p(d_abund), n_sample, C.c_void_p(d_w_overlap),
                                              C.c_void_p(d_w_match), C.c_void_p(d_med)))
+
+    def explain(self, sample, member, abund=None, want_flags: bool = True) -> Tuple[Optional[np.ndarray], np.ndarray]:
+        """What the call sets of `member` explain of the sample (yh_explain).  member: uint8 [n_refs], bit k (0..6) = the
+        reference belongs to call set k.  abund: one abundance per sample hash, or None (all 1).  Returns (flags, totals):
+        flags uint8 [n], 0 for a hash no reference holds, else 0x80 | OR of the member bytes of all its holders (None with
+        want_flags=False: the totals only); totals uint64 [8, 2], per bit the number of sample hashes whose flag has it set
+        and the sum of their abundances."""
+        if abund is None:
+            sample = _as_u64(sample)
+        else:
+            sample, abund = check_abundances(sample, abund)
+        member = check_member(member, self.n_refs)
+        flags = np.zeros(sample.size, dtype=np.uint8) if want_flags else None
+        totals = np.zeros((8, 2), dtype=np.uint64)
+        _lib.check(self._lib.yh_explain(self._h, _ptr(sample), _ptr(abund), sample.size, _ptr(member), _ptr(flags), _ptr(totals)))
+        return flags, totals
+
+    def explain_device(self, d_sample: int, d_abund: int, n_sample: int, d_member: int, d_flags: int, d_totals: int) -> None:
+        """yh_explain_device: uint64 sample, uint32 abundances (0: all 1) and uint8 [N] member table in, uint8 [n_sample]
+        flags (0: none) and uint64 [8][2] totals out."""
+        _lib.check(self._lib.yh_explain_device(self._h, C.c_void_p(d_sample), C.c_void_p(d_abund), n_sample, C.c_void_p(d_member),
+                                               C.c_void_p(d_flags), C.c_void_p(d_totals)))
 
     # sharded run (dist.ShardedRefDB): the step in two halves around the exchange of the subset bits
     def set_ghosts(self, ghost_begin: int, n_ghost: int, d_ghost_src: int) -> None:

@@ -51,6 +51,14 @@ ARGUMENTS = (
                          help="Also estimate how much of each organism the sample holds: the depth (sum, mean, median of the "
                               "sample's per-hash abundances) over the k-mers exclusive to each genome, as extra columns of "
                               "every table and as results/abundance_profile.tsv.  Needs a sample sketched with abundances.")),
+    ("--residual", dict(action="store_true",
+                        help="Also report what of the sample the organisms called present explain: results/sample_explained.tsv "
+                             "(per min_coverage: sample hashes and abundance in the database, explained by the call set, and "
+                             "left over) and results/residual.sig.zip, the sample restricted to the hashes the call set of "
+                             "--residual_coverage does not explain, ready for another `yacht run`.")),
+    ("--residual_coverage", dict(type=float, default=None,
+                                 help="The --min_coverage_list value whose call set results/residual.sig.zip is taken for "
+                                      "(with --residual; default: the smallest value of the list).")),
 )
 
 # messages the reference raises with (callers and its tests match on them)
@@ -134,6 +142,11 @@ def decompress_legacy_db(genome_dir: str, num_threads: int) -> None:
 
 def main(args) -> None:
     files = [args.sample_file] if isinstance(args.sample_file, str) else list(args.sample_file)
+    want_residual = bool(getattr(args, "residual", False))
+    if want_residual or getattr(args, "residual_coverage", None) is not None:
+        from . import residual
+
+        residual_cov = residual.residual_coverage(args)  # (ValueError before anything is written or any device work)
     if len(files) > 1:
         from . import cohort
 
@@ -193,6 +206,12 @@ def main(args) -> None:
         results = hr.hypothesis_recovery(manifest, (sample_file, sample_sig), genome_dir, covs, scale, ksize,
                                          args.significance, ani_thresh, args.num_threads,
                                          **({"abundances": sample_abund} if want_abundance else {}))
+    if want_residual:  # one more call on the still-resident database: the call sets are this run's presence calls
+        with phases.phase("explain"):
+            user_covs = covs if has_raw else covs[1:]
+            call_sets = residual.call_sets_of(manifest["organism_name"], results if has_raw else results[1:])
+            explained = residual.explain_call_sets(hr._LAST_RUN["db"], hr._LAST_RUN["mins"],
+                                                   residual.sample_abundances_or_none(sample_sig), call_sets)
     hr.release_reference_dbs()
     results = trim_results(results)
 
@@ -202,6 +221,8 @@ def main(args) -> None:
     write_sample_results(results, covs, has_raw, results_folder, args.keep_raw, args.show_all)
     if want_abundance:
         abundance.write_profile(results if has_raw else results[1:], covs if has_raw else covs[1:], results_folder)
+    if want_residual:
+        residual.write_outputs(results_folder, sample_sig, user_covs, call_sets, *explained, residual_cov)
     _t_write.__exit__(None, None, None)
 
 
