@@ -52,8 +52,8 @@ def _load_le(b: np.ndarray, start: int, n: int) -> np.ndarray:
     return out
 
 
-def murmur3_x64_128_h1(b: np.ndarray, seed: int = 42) -> np.ndarray:
-    """First 64 bits of MurmurHash3_x64_128 for every row of the uint8 matrix b (equal lengths)."""
+def murmur3_x64_128(b: np.ndarray, seed: int = 42) -> Tuple[np.ndarray, np.ndarray]:
+    """Both 64-bit words (h1, h2) of MurmurHash3_x64_128 for every row of the uint8 matrix b (equal lengths)."""
     with np.errstate(over="ignore"):
         n, length = b.shape
         h1 = np.full(n, seed, dtype=np.uint64)
@@ -82,7 +82,14 @@ def murmur3_x64_128_h1(b: np.ndarray, seed: int = 42) -> np.ndarray:
         h2 = h2 + h1
         h1 = _fmix(h1)
         h2 = _fmix(h2)
-        return h1 + h2
+        h1 = h1 + h2
+        h2 = h2 + h1
+        return h1, h2
+
+
+def murmur3_x64_128_h1(b: np.ndarray, seed: int = 42) -> np.ndarray:
+    """First 64 bits of MurmurHash3_x64_128 for every row of the uint8 matrix b (equal lengths)."""
+    return murmur3_x64_128(b, seed)[0]
 
 
 _CODE = np.full(256, 4, dtype=np.uint8)

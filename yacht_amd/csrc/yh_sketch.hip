@@ -14,6 +14,7 @@
 
 namespace {
 
+// (tests/test_gpu_sketch_edges.py restates SK_THREADS * SK_ITEMS, SK_LCAP, RL_RUN, RL_WIN and the 16-base unit: keep it in step)
 constexpr int SK_THREADS = 256;
 constexpr int SK_ITEMS = 8;      // windows per lane
 constexpr int SK_LCAP = 2048;    // kept hashes parked in LDS per workgroup before the flush
