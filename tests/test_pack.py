@@ -1,5 +1,6 @@
 """The packed sample format (yh_sample_pack / yh_sample_unpack, host code of the C ABI): round trips, sizes, refusals.
-No GPU needed.  The device-side expansion and the compact rows are checked in tests/test_gpu_pipeline.py."""
+No GPU needed.  The device-side expansion and the compact rows are checked in tests/test_gpu_pipeline.py and, at the edges
+of the formats, in tests/test_gpu_packed_edges.py."""
 import numpy as np
 import pytest
 

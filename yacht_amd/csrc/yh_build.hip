@@ -817,9 +817,13 @@ static int upload_sorted_impl(yh_db* db, const u64* h_values, const u64* h_offse
         if (copy_failed.load()) { yh_set_error("CSR upload failed"); rc = YH_ERR_HIP; break; }
         UP_HIP(hipStreamWaitEvent(st, ev[c], 0));
         UP_HIP(hipEventRecord(eb[c], st));
-        if (rc == YH_OK && pk)
+        if (rc == YH_OK && pk) {
             rc = yh_csr_expand_device(db, d_pk_tab, d_pk_payload, pk->payload_words, d_pk_fb, d_offsets, N, pk->first_block[r0], pk->first_block[r1],
                                       d_values, db->d_flag);
+            if (trace_on())  // (which expansion ran: the tests of k_unpack_csr assert on this line)
+                fprintf(stderr, "[yh build] packed chunk %zu of %zu: references [%llu, %llu), blocks [%llu, %llu) expanded on the device\n", c + 1, C,
+                        r0, r1, pk->first_block[r0], pk->first_block[r1]);
+        }
         if (rc == YH_OK) rc = validate_refs(db, d_values, d_offsets, r0, r1);
         if (rc == YH_OK && n && pc) {
             rc = yh_pc_scan(db, pc, d_values, db->d_fz_off, r0, r1, n, false);  // (k_scan_refs above checked the order)
