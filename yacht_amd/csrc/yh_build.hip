@@ -1201,6 +1201,7 @@ int yh_build_index(yh_db* db, const u64* d_values, const u64* d_offsets, u64* d_
         // a bucket spans ceil(2^bits / mul) hash values: the low 32 bits identify a hash inside it iff that is <= 2^32
         const bool compact = full && !wide_env && nb_c <= 0xfffffff0ull && mul_c > 0 &&
                              (bits <= 32 || (((unsigned __int128)1 << bits) + mul_c - 1) / mul_c <= ((unsigned __int128)1 << 32));
+        u64 n_over = 0, ovf_cap = 0;  // (compact: entries and capacity of the overflow table)
         u64* d_dh_tmp = nullptr;   // compact: dh / dref are build-time temporaries
         u32* d_dref_tmp = nullptr;
         if (full && !compact && db->n_distinct > 0x7ffffff0ull) {  // (the five-entry form indexes the distinct hashes with 32 bits)
@@ -1244,7 +1245,6 @@ int yh_build_index(yh_db* db, const u64* d_values, const u64* d_offsets, u64* d_
         if (rc == YH_OK && compact) {
             db->cbkt_nb = nb_c;
             db->bkt_mul = mul_c;
-            u64 n_over = 0;
             u64* d_cnt = reinterpret_cast<u64*>(d_counts);  // (free again: the per-block counts were consumed by k_idx_emit)
             IDX_HIP(hipMemsetAsync(d_cnt, 0, sizeof(u64), st));
             if (rc == YH_OK)
@@ -1255,6 +1255,7 @@ int yh_build_index(yh_db* db, const u64* d_values, const u64* d_offsets, u64* d_
             while (cap < 2 * n_over + 16) cap <<= 1;
             if (cap > (1ull << 31)) { yh_set_error("overflow table too large"); rc = YH_ERR_UNSUPPORTED; }
             db->ovf_mask = (u32)(cap - 1);
+            ovf_cap = cap;
             if (rc == YH_OK) rc = yh_dmalloc(db, (void**)&db->d_cbkt, nb_c * 64);
             if (rc == YH_OK) rc = yh_dmalloc(db, (void**)&db->d_ovf_keys, cap * sizeof(u64));
             if (rc == YH_OK) rc = yh_dmalloc(db, (void**)&db->d_ovf_vals, cap * sizeof(u32));
@@ -1288,6 +1289,11 @@ int yh_build_index(yh_db* db, const u64* d_values, const u64* d_offsets, u64* d_
         }
         IDX_HIP(hipStreamSynchronize(st));
         TRACE("index: emit + table + filter");
+        if (trace_on() && rc == YH_OK && full)  // (which form the directory took: the tests of the lookup kernels assert on this line)
+            fprintf(stderr, "[yh build] directory form %s: nb %llu mul %llu overflow %llu of %llu filter bits %llu\n",
+                    compact ? "compact" : db->d_bkt ? "wide" : "directory", (unsigned long long)(compact ? db->cbkt_nb : db->bkt_nb),
+                    (unsigned long long)db->bkt_mul, (unsigned long long)n_over, (unsigned long long)ovf_cap,
+                    (unsigned long long)db->filter_bits);
         yh_tfree(db, d_dh_tmp);
         yh_tfree(db, d_dref_tmp);
         if (rc == YH_OK && full) db->has_dir = true;
