@@ -9,8 +9,8 @@
 // the sample and in no OTHER reference of the run subset (overlap > 0).  A sample hash held by j and k gives both of
 // them overlap, so both are in the subset: a SAMPLE hash is exclusive to j exactly when j is its only holder in the
 // database -- its dref word has the top bit clear (YhDirView::find).  The same holds for any superset of the subset.
-// So this pass needs no subset bits, no step context, no batch slot and no exclusive work list: it is the indexed
-// lookup (yh_query.hip: lookup_tile_body) with "+= a(h)" in place of "+= 1", and the posting list of a shared hash
+// So this pass needs no subset bits, no step context, no batch slot and no exclusive work list: it is the directory
+// probe of yh_lookup.h with "+= a(h)" in place of the indexed lookup's "+= 1", and the posting list of a shared hash
 // feeds w_overlap only.  (With ghosts registered exclusivity is not local to the handle: the entry refuses.)
 //
 // Layout: k_abund_lookup (tiles of THREADS x U sample hashes, all filter reads then all bucket reads in flight, hits summed
@@ -19,6 +19,7 @@
 // workgroup) -> rocprim::radix_sort_keys over the (reference << 32 | a) keys of those hits -> k_abund_median (one lane per reference, two lower-bound searches).  The last two only when the
 // caller asks for the median.
 #include "yh_abund.h"
+#include "yh_lookup.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -40,21 +41,6 @@ struct AbundLookup {
     u64* keys;     // [n] (reference << 32) | a of every single-holder hit, in arrival order; null: no median wanted
     u64* n_hits;   // [1] keys appended so far (one atomic per workgroup)
 };
-
-// The posting list of a shared hash found in the sample, holders requested four at a time (the walk of yh_query.hip's
-// lookup: a list of 8 would otherwise be 8 dependent round trips).
-template <typename Add>
-__device__ __forceinline__ void walk_holders(const u64* __restrict__ po, const u32* __restrict__ pr, u32 gi, Add add) {
-    const u64 q0 = po[gi], qe = po[gi + 1];
-    for (u64 q = q0; q < qe; q += 4) {
-        u32 h[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) h[i] = pr[min(q + (u64)i, qe - 1)];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (q + (u64)i < qe) add(h[i]);
-    }
-}
 
 // (tkey: reference + 1, 0 = empty; tov / tmt: the two sums of that reference in this workgroup's tile)
 template <int U, int THREADS, int TBITS>
@@ -85,51 +71,23 @@ __global__ void __launch_bounds__(THREADS) k_abund_lookup(const AbundLookup q) {
     }
     for (u32 k = threadIdx.x; k < TSLOTS; k += THREADS) { tkey[k] = 0; tov[k] = 0; tmt[k] = 0; }
     if (threadIdx.x == 0) wg_hits = 0;
-    YhDirView::v4u a[U], b[U], c[U], d[U];
+    YhProbe<U> probe;
     u32 r[U];
-    if (filter) {  // the presence bits first: a hash whose bits are clear is not in the database (yh_db::d_filter)
-        u64 bit[U];
-        u32 w[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            bit[u] = yh_bucket_of(h[u], dv.bkt_lsh, q.filter_mul);
-            w[u] = filter[bit[u] >> 5];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const u32 m = yh_filter_mask(h[u], bit[u]);
-            ok[u] = ok[u] && (w[u] & m) == m;
-        }
-    }
-    if (dv.cbkt) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            a[u] = b[u] = c[u] = d[u] = YhDirView::v4u{0u, 0u, 0u, 0u};
-            if (ok[u]) dv.cbkt_request(h[u], a[u], b[u], c[u], d[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) asm volatile("" : "+v"(a[u]), "+v"(b[u]), "+v"(c[u]), "+v"(d[u]));  // (see YhDirView::find)
-    }
+    yh_probe_filter<U>(dv, filter, q.filter_mul, h, ok);
+    yh_probe_request<U>(dv, h, ok, probe);
     __syncthreads();  // the table is clear
     auto add = [&](u32 ref, u64 v, bool only_holder) {
-        u32 slot = (ref * 2654435761u) >> (32 - TBITS);
-#pragma unroll 1
-        for (int probe = 0; probe < 2; ++probe, slot = (slot + 1) & (TSLOTS - 1)) {
-            const u32 old = atomicCAS(&tkey[slot], 0u, ref + 1);
-            if (old == 0 || old == ref + 1) {
-                atomicAdd(&tov[slot], v);
-                if (only_holder) atomicAdd(&tmt[slot], v);
-                return;
-            }
+        const int slot = yh_hit_slot<TBITS>(tkey, ref);
+        if (slot >= 0) {
+            atomicAdd(&tov[slot], v);
+            if (only_holder) atomicAdd(&tmt[slot], v);
+            return;
         }
         atomicAdd(&q.w_overlap[ref], v);  // crowded table: sum directly
         if (only_holder) atomicAdd(&q.w_match[ref], v);
     };
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-        r[u] = YH_DIR_NONE;
-        if (ok[u]) r[u] = dv.cbkt ? dv.cbkt_resolve(h[u], a[u], b[u], c[u], d[u]) : dv.find(h[u]);
-    }
+    for (int u = 0; u < U; ++u) r[u] = yh_probe_resolve<U>(dv, h, ok, probe, u);
     // The places of the single-holder hits in the hit buffer, aggregated twice: a wave's hits take consecutive places
     // (ballot; one returning LDS atomic per wave), and the workgroup claims all of its places with ONE returning global
     // atomic on the device counter.  (One global atomic per wave -- 15 600 of them on one address for a 10^6-hash sample,
@@ -240,19 +198,14 @@ int yh_q_abund(yh_db* db, const u64* d_sample, const u32* d_abund, u64 n_sample,
             if (hipMemsetAsync(d_keys, 0xff, n_sample * sizeof(u64), st) != hipSuccess ||
                 hipMemsetAsync(d_count, 0, 16, st) != hipSuccess) { yh_set_error("hipMemsetAsync failed"); rc = YH_ERR_HIP; break; }
         }
-        const AbundLookup q{d_sample, d_abund, n_sample, yh_dir_view(db), nullptr, db->filter_mul, db->d_po, db->d_pr,
-                            d_w_overlap, d_w_match, d_keys, d_count};
-        // the tile shapes of the indexed lookup (yh_q_overlap_indexed): small samples are latency-bound and read no filter
-#define YH_ABUND_LAUNCH(UU, TT, BB, FILTER)                                                                          \
-    do {                                                                                                             \
-        AbundLookup ql = q;                                                                                          \
-        ql.filter = FILTER;                                                                                          \
-        k_abund_lookup<UU, TT, BB><<<(u32)((n_sample + (u64)(TT) * (UU) - 1) / ((u64)(TT) * (UU))), TT, 0, st>>>(ql); \
-    } while (0)
-        if (n_sample >= 512ull * 1024) YH_ABUND_LAUNCH(2, 1024, 10, yh_filter_of(db));
-        else if (n_sample >= 256ull * 1024) YH_ABUND_LAUNCH(1, 1024, 10, yh_filter_of(db));
-        else YH_ABUND_LAUNCH(1, 256, 8, nullptr);
-#undef YH_ABUND_LAUNCH
+        const YhTileShape shape = yh_tile_shape_for(n_sample);
+        const AbundLookup q{d_sample, d_abund, n_sample, yh_dir_view(db), shape.filter ? yh_filter_of(db) : nullptr, db->filter_mul,
+                            db->d_po, db->d_pr, d_w_overlap, d_w_match, d_keys, d_count};
+        switch (shape.form) {
+        case 2: k_abund_lookup<2, 1024, 10><<<shape.tiles(n_sample), 1024, 0, st>>>(q); break;
+        case 1: k_abund_lookup<1, 1024, 10><<<shape.tiles(n_sample), 1024, 0, st>>>(q); break;
+        default: k_abund_lookup<1, 256, 8><<<shape.tiles(n_sample), 256, 0, st>>>(q); break;
+        }
         if (d_med_match) {
             if (rocprim::radix_sort_keys(d_tmp, tmp_bytes, (const u64*)d_keys, d_sorted, (size_t)n_sample, 0u, end_bit, st) != hipSuccess) {
                 yh_set_error("radix sort failed: %s", hipGetErrorString(hipGetLastError())); rc = YH_ERR_HIP; break;

@@ -1,5 +1,5 @@
 // yh_batch.hip -- batched `yacht run`: up to 256 samples against the resident database in one pass
-#include "yh_common.h"
+#include "yh_lookup.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -99,20 +99,16 @@ __global__ void __launch_bounds__(256) k_batch_lookup(const u64* __restrict__ sa
             if (ref == 0x7ffffff1u) row[0] = 1;
             return;
 #endif
-            u32 slot = (ref * 2654435761u) >> (32 - BATCH_TBITS);
 #if defined(YH_BATCH_DIRECT_ATOMICS) && YH_BATCH_DIRECT_ATOMICS  // measurement build: one global atomic per hit, no LDS table (results right)
             atomicAdd(&row[ref], 1u);
             if (shared) atomicAdd(&row2[ref], 1u);
             return;
 #endif
-#pragma unroll 1
-            for (int probe = 0; probe < 2; ++probe, slot = (slot + 1) & (TSLOTS - 1)) {
-                const u32 old = atomicCAS(&tkey[slot], 0u, ref + 1);
-                if (old == 0 || old == ref + 1) {
-                    atomicAdd(&tcnt[slot], 1u);
-                    if (shared) atomicAdd(&tcnt2[slot], 1u);
-                    return;
-                }
+            const int slot = yh_hit_slot<BATCH_TBITS>(tkey, ref);
+            if (slot >= 0) {
+                atomicAdd(&tcnt[slot], 1u);
+                if (shared) atomicAdd(&tcnt2[slot], 1u);
+                return;
             }
             atomicAdd(&row[ref], 1u);  // crowded table: count directly
             if (shared) atomicAdd(&row2[ref], 1u);
@@ -136,9 +132,7 @@ __global__ void __launch_bounds__(256) k_batch_lookup(const u64* __restrict__ sa
         for (u64 k0 = i * BATCH_TILE; k0 < k_end; k0 += 256u * BATCH_U) {  // (workgroup-uniform)
             u64 h[BATCH_U];
             bool ok[BATCH_U];
-            u32 w[BATCH_U];
-            u64 bit[BATCH_U];
-            YhDirView::v4u a[BATCH_U], b[BATCH_U], c[BATCH_U], d[BATCH_U];
+            YhProbe<BATCH_U> probe;
 #pragma unroll
             for (int u = 0; u < BATCH_U; ++u) {
                 const u64 k = k0 + (u64)u * 256u + threadIdx.x;
@@ -150,48 +144,30 @@ __global__ void __launch_bounds__(256) k_batch_lookup(const u64* __restrict__ sa
                 ok[u] = k < k_end && h[u] <= dv.max_hash;
                 if (!ok[u]) h[u] = 0;  // (still a valid word / bucket to read)
             }
-#if defined(YH_ABLATE_BATCH_READS) && (YH_ABLATE_BATCH_READS & 2)
-            if (false) {
+#if defined(YH_ABLATE_BATCH_READS) && (YH_ABLATE_BATCH_READS & 2)  // timing-only build: no filter word is read (see below)
+            const u32* const probe_filter = nullptr;
 #else
-            if (filter) {
+            const u32* const probe_filter = filter;
 #endif
-#pragma unroll
-                for (int u = 0; u < BATCH_U; ++u) {
-                    bit[u] = yh_bucket_of(h[u], dv.bkt_lsh, filter_mul);
-                    w[u] = filter[bit[u] >> 5];
-                }
-#pragma unroll
-                for (int u = 0; u < BATCH_U; ++u) {
-                    const u32 m = yh_filter_mask(h[u], bit[u]);
-                    ok[u] = ok[u] && (w[u] & m) == m;
+            yh_probe_filter<BATCH_U>(dv, probe_filter, filter_mul, h, ok);
 #if defined(YH_ABLATE_BATCH_READS) && (YH_ABLATE_BATCH_READS & 1)  // timing-only build: the filter word is read, no bucket is (results wrong)
-                    ok[u] = ok[u] && h[u] == 0x123456789abcdefull;
-#endif
-                }
+            if (probe_filter) {
+#pragma unroll
+                for (int u = 0; u < BATCH_U; ++u) ok[u] = ok[u] && h[u] == 0x123456789abcdefull;
             }
-#if defined(YH_ABLATE_BATCH_READS) && (YH_ABLATE_BATCH_READS & 2)  // timing-only build: no filter word is read; the hashes that WOULD pass a
+#endif
+#if defined(YH_ABLATE_BATCH_READS) && (YH_ABLATE_BATCH_READS & 2)  // timing-only build: the hashes that WOULD pass a
             // perfect filter are not known, so every fourth hash reads its bucket (0.25 per hash: the bench samples' 0.27 + none of the 0.12 false positives)
 #pragma unroll
             for (int u = 0; u < BATCH_U; ++u) ok[u] = ok[u] && ((h[u] >> 7) & 3ull) == 0;
 #endif
-            if (dv.cbkt) {
-#pragma unroll
-                for (int u = 0; u < BATCH_U; ++u) {
-                    a[u] = b[u] = c[u] = d[u] = YhDirView::v4u{0u, 0u, 0u, 0u};
 #if defined(YH_BATCH_NT) && (YH_BATCH_NT & 1)
-                    if (ok[u]) dv.cbkt_request_nt(h[u], a[u], b[u], c[u], d[u]);
+            yh_probe_request<BATCH_U, true>(dv, h, ok, probe);
 #else
-                    if (ok[u]) dv.cbkt_request(h[u], a[u], b[u], c[u], d[u]);
+            yh_probe_request<BATCH_U, false>(dv, h, ok, probe);
 #endif
-                }
 #pragma unroll
-                for (int u = 0; u < BATCH_U; ++u) asm volatile("" : "+v"(a[u]), "+v"(b[u]), "+v"(c[u]), "+v"(d[u]));  // (see YhDirView::find)
-            }
-#pragma unroll
-            for (int u = 0; u < BATCH_U; ++u) {
-                if (!ok[u]) continue;
-                hits_of(dv.cbkt ? dv.cbkt_resolve(h[u], a[u], b[u], c[u], d[u]) : dv.find(h[u]));
-            }
+            for (int u = 0; u < BATCH_U; ++u) hits_of(yh_probe_resolve<BATCH_U>(dv, h, ok, probe, u));
         }
         __syncthreads();
         for (u32 k = threadIdx.x; k < TSLOTS; k += 256)

@@ -5,13 +5,13 @@
 //   flags[h]     = 0 when no reference of the database holds h, else 0x80 | OR of member[j] over ALL holders j of h
 //   totals[b][0] = number of sample hashes whose flag has bit b set,  totals[b][1] = sum of a(h) over the same hashes
 // Every other query of the library reduces over the sample and answers [N] arrays; this one answers [n_sample].  It is the
-// indexed lookup again (yh_query.hip: lookup_tile_body; yh_abund.hip: k_abund_lookup) -- the same tile shapes, the same
-// filter and bucket reads in flight -- with a simpler tail: no LDS hit table and no per-reference atomics.  A single-holder
-// hit reads ONE byte of the member table (N bytes: it stays in the L2), a shared hit ORs the bytes of its posting list, and
+// directory probe of yh_lookup.h again -- the tile shapes, the filter and bucket reads in flight -- with a simpler tail than
+// the indexed lookup's: no LDS hit table and no per-reference atomics.  A single-holder hit reads ONE byte of the member table (N bytes: it stays in the L2), a shared hit ORs the bytes of its posting list, and
 // each lane stores its own byte (consecutive lanes, consecutive bytes).  The totals are reduced in the wave (a ballot and a
 // popcount per bit; a wave sum of the abundances, only for the bits that some lane of the wave has set), then in LDS, and
 // leave as at most 16 global atomics per workgroup.  Integer adds and ORs: the result does not depend on arrival order.
 #include "yh_explain.h"
+#include "yh_lookup.h"
 
 namespace {
 
@@ -30,7 +30,7 @@ struct ExplainLookup {
 };
 
 // OR of the member bytes over the posting list of a shared hash, holders requested four at a time and their four member
-// bytes after them (the walk of yh_query.hip's lookup).  The clamped tail re-reads the last holder: harmless under OR.
+// bytes after them (as walk_holders, yh_lookup.h).  The clamped tail re-reads the last holder: harmless under OR.
 __device__ __forceinline__ u32 or_holders(const u64* __restrict__ po, const u32* __restrict__ pr, const u8* __restrict__ member, u32 gi) {
     const u64 q0 = po[gi], qe = po[gi + 1];
     u32 m = 0;
@@ -74,36 +74,14 @@ __global__ void __launch_bounds__(THREADS) k_explain_lookup(const ExplainLookup 
         if (!ok[u]) h[u] = 0;  // (still a valid bucket to read)
     }
     if (threadIdx.x < 16) wg_tot[threadIdx.x] = 0;
-    YhDirView::v4u a[U], b[U], c[U], d[U];
-    if (filter) {  // the presence bits first: a hash whose bits are clear is not in the database (yh_db::d_filter)
-        u64 bit[U];
-        u32 w[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            bit[u] = yh_bucket_of(h[u], dv.bkt_lsh, q.filter_mul);
-            w[u] = filter[bit[u] >> 5];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const u32 m = yh_filter_mask(h[u], bit[u]);
-            ok[u] = ok[u] && (w[u] & m) == m;
-        }
-    }
-    if (dv.cbkt) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            a[u] = b[u] = c[u] = d[u] = YhDirView::v4u{0u, 0u, 0u, 0u};
-            if (ok[u]) dv.cbkt_request(h[u], a[u], b[u], c[u], d[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) asm volatile("" : "+v"(a[u]), "+v"(b[u]), "+v"(c[u]), "+v"(d[u]));  // (see YhDirView::find)
-    }
+    YhProbe<U> probe;
+    yh_probe_filter<U>(dv, filter, q.filter_mul, h, ok);
+    yh_probe_request<U>(dv, h, ok, probe);
     __syncthreads();  // wg_tot is clear
     u32 f[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        u32 r = YH_DIR_NONE;
-        if (ok[u]) r = dv.cbkt ? dv.cbkt_resolve(h[u], a[u], b[u], c[u], d[u]) : dv.find(h[u]);
+        const u32 r = yh_probe_resolve<U>(dv, h, ok, probe, u);
         f[u] = 0;
         if (r != YH_DIR_NONE) {
             const u32 m = (r & 0x80000000u) ? or_holders(q.po, q.pr, member, r & 0x7fffffffu) : (u32)member[r];
@@ -147,19 +125,14 @@ int yh_q_explain(yh_db* db, const u64* d_sample, const u32* d_abund, u64 n_sampl
     hipStream_t st = db->stream;
     k_explain_clear<<<1, 64, 0, st>>>(d_totals);
     if (n_sample != 0 && db->n_refs != 0 && db->n_distinct != 0) {
-        const ExplainLookup q{d_sample, d_abund, n_sample, yh_dir_view(db), nullptr, db->filter_mul, db->d_po, db->d_pr,
-                              d_member, d_flags, d_totals};
-        // the tile shapes of the indexed lookup (yh_q_overlap_indexed): small samples are latency-bound and read no filter
-#define YH_EXPLAIN_LAUNCH(UU, TT, FILTER)                                                                          \
-    do {                                                                                                           \
-        ExplainLookup ql = q;                                                                                      \
-        ql.filter = FILTER;                                                                                        \
-        k_explain_lookup<UU, TT><<<(u32)((n_sample + (u64)(TT) * (UU) - 1) / ((u64)(TT) * (UU))), TT, 0, st>>>(ql); \
-    } while (0)
-        if (n_sample >= 512ull * 1024) YH_EXPLAIN_LAUNCH(2, 1024, yh_filter_of(db));
-        else if (n_sample >= 256ull * 1024) YH_EXPLAIN_LAUNCH(1, 1024, yh_filter_of(db));
-        else YH_EXPLAIN_LAUNCH(1, 256, nullptr);
-#undef YH_EXPLAIN_LAUNCH
+        const YhTileShape shape = yh_tile_shape_for(n_sample);
+        const ExplainLookup q{d_sample, d_abund, n_sample, yh_dir_view(db), shape.filter ? yh_filter_of(db) : nullptr, db->filter_mul,
+                              db->d_po, db->d_pr, d_member, d_flags, d_totals};
+        switch (shape.form) {
+        case 2: k_explain_lookup<2, 1024><<<shape.tiles(n_sample), 1024, 0, st>>>(q); break;
+        case 1: k_explain_lookup<1, 1024><<<shape.tiles(n_sample), 1024, 0, st>>>(q); break;
+        default: k_explain_lookup<1, 256><<<shape.tiles(n_sample), 256, 0, st>>>(q); break;
+        }
     }
     if (hipGetLastError() != hipSuccess) { yh_set_error("explain launch failed"); return YH_ERR_HIP; }
     return YH_OK;

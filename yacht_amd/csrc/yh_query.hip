@@ -15,7 +15,7 @@
 //                        k_excl_final (the arithmetic of hypothesis_recovery_src.py:165-204)
 //   k_overlap_bsearch    one wave per reference, lanes binary-search the sample: the independent cross-check
 // (the batched run is yh_batch.hip, `yacht train`'s pairwise counts yh_pairwise.hip)
-#include "yh_common.h"
+#include "yh_lookup.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -823,38 +823,16 @@ __global__ void __launch_bounds__(256) k_overlap_bsearch(const u64* __restrict__
 // its holder (or the posting list of a shared hash) -> replicated counters.  Work is proportional
 // to |S|, not to the database: ~3 dependent memory round trips per sample hash instead of
 // streaming every reference hash.  Also flags the shared hashes found (hit[], for R2).
-// The posting list of a shared hash found in the sample: every holder counts one hit.  The holders are requested
-// four at a time (a list of 8 was 8 dependent round trips: the tail of the launch for a sample of cluster members).
-template <typename Add>
-__device__ __forceinline__ void walk_holders(const u64* __restrict__ po, const u32* __restrict__ pr, u32 gi, Add add) {
-    const u64 q0 = po[gi], qe = po[gi + 1];
-    for (u64 q = q0; q < qe; q += 4) {
-        u32 h[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) h[i] = pr[min(q + (u64)i, qe - 1)];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (q + (u64)i < qe) add(h[i]);
-    }
-}
-
-// The same lookup for LARGE samples: a workgroup of IDX_THREADS lanes takes a tile of IDX_THREADS x U consecutive
+// The same lookup for LARGE samples: a workgroup of 1024 lanes takes a tile of 1024 x U consecutive
 // sample hashes, every lane has its U bucket reads in flight together, and the hits are summed per reference in an
 // LDS table that leaves as ONE global atomic per (workgroup, reference) at the end.  In hash order the hits of a
 // genome that is really in the sample (thousands of them) are spread evenly over the workgroups, and same-address
 // atomics are serialized memory-side: with one atomic per hit the hottest counter is the tail of the launch (one
 // 10^6-hash sample repeated, so that its buckets stay in the Infinity Cache: 1.9e5 hits on 284 references 35.1 us, no
 // hit at all 25.1 us, tiles 29.8 us; rotating samples, buckets from HBM: 38-40 -> 36 us, no hit 32).
-#ifndef YH_IDX_THREADS
-#define YH_IDX_THREADS 1024
-#endif
-#ifndef YH_IDX_TBITS
-#define YH_IDX_TBITS 10
-#endif
-constexpr int IDX_THREADS = YH_IDX_THREADS;
-// (THREADS lanes x U hashes per workgroup, 2^TBITS slots in the hit table: <2, 1024, 10> for large samples; <1, 256, 8>
-// for small ones, where the table keeps a sample that is mostly ONE genome -- an isolate -- from sending thousands of
-// atomics to one counter)
+// (THREADS lanes x U hashes per workgroup, 2^TBITS slots in the hit table: the shapes of YhTileShape, yh_lookup.h.  For
+// small samples the table keeps one that is mostly ONE genome -- an isolate -- from sending thousands of atomics to one
+// counter.)
 struct TileLookup {
     const u64* sample;
     u64 n;
@@ -899,61 +877,38 @@ __device__ __forceinline__ void lookup_tile_body(u32 wg, u32* tkey, u32* tcnt, u
     if (q.bad && *q.bad == q.bad_gen) return;
 #endif
     for (u32 k = threadIdx.x; k < TSLOTS; k += THREADS) { tkey[k] = 0; tcnt[k] = 0; tcnt2[k] = 0; }
-    YhDirView::v4u a[U], b[U], c[U], d[U];
+    YhProbe<U> probe;
     u32 r[U];
 #if defined(YH_ABLATE_LOOKUP) && (YH_ABLATE_LOOKUP & 16)  // timing-only build: no presence filter read
-    if (false) {
+    yh_probe_filter<U>(dv, nullptr, q.filter_mul, h, ok);
 #else
-    if (filter) {  // the presence bits first: a hash whose bit is clear is not in the database (yh_db::d_filter)
+    yh_probe_filter<U>(dv, filter, q.filter_mul, h, ok);
 #endif
-        u64 bit[U];
-        u32 w[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            bit[u] = yh_bucket_of(h[u], dv.bkt_lsh, q.filter_mul);
-            w[u] = filter[bit[u] >> 5];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const u32 m = yh_filter_mask(h[u], bit[u]);
-            ok[u] = ok[u] && (w[u] & m) == m;
-        }
-    }
+#if defined(YH_ABLATE_LOOKUP) && (YH_ABLATE_LOOKUP & 8)  // timing-only build: no bucket is read (every hash "absent" behind the filter)
     if (dv.cbkt) {
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            a[u] = b[u] = c[u] = d[u] = YhDirView::v4u{0u, 0u, 0u, 0u};
-#if defined(YH_ABLATE_LOOKUP) && (YH_ABLATE_LOOKUP & 8)  // timing-only build: no bucket is read (every hash "absent" behind the filter)
-            ok[u] = ok[u] && h[u] == 0x123456789abcdefull;
-#endif
-            if (ok[u]) dv.cbkt_request(h[u], a[u], b[u], c[u], d[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) asm volatile("" : "+v"(a[u]), "+v"(b[u]), "+v"(c[u]), "+v"(d[u]));  // (see YhDirView::find)
+        for (int u = 0; u < U; ++u) ok[u] = ok[u] && h[u] == 0x123456789abcdefull;
     }
+#endif
+    yh_probe_request<U>(dv, h, ok, probe);
     __syncthreads();  // the table is clear
     auto add = [&](u32 ref, bool shared) {
 #if defined(YH_ABLATE_LOOKUP) && (YH_ABLATE_LOOKUP & 4)  // timing-only build: hits are not counted
         if (ref == 0x7ffffff1u) my[0] = 1;
         return;
 #endif
-        u32 slot = (ref * 2654435761u) >> (32 - TBITS);
-#pragma unroll 1
-        for (int probe = 0; probe < 2; ++probe, slot = (slot + 1) & (TSLOTS - 1)) {
-            const u32 old = atomicCAS(&tkey[slot], 0u, ref + 1);
-            if (old == 0 || old == ref + 1) {
-                atomicAdd(&tcnt[slot], 1u);
-                if (shared && my2) atomicAdd(&tcnt2[slot], 1u);
-                return;
-            }
+        const int slot = yh_hit_slot<TBITS>(tkey, ref);
+        if (slot >= 0) {
+            atomicAdd(&tcnt[slot], 1u);
+            if (shared && my2) atomicAdd(&tcnt2[slot], 1u);
+            return;
         }
         count_add(&my[ref], 1u);  // crowded table: count directly
         if (shared && my2) count_add(&my2[ref], 1u);
     };
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        r[u] = YH_DIR_NONE;
-        if (ok[u]) r[u] = dv.cbkt ? dv.cbkt_resolve(h[u], a[u], b[u], c[u], d[u]) : dv.find(h[u]);
+        r[u] = yh_probe_resolve<U>(dv, h, ok, probe, u);
         if (r[u] == YH_DIR_NONE) continue;
         if (!(r[u] & 0x80000000u)) {
             add(r[u], false);
@@ -1435,7 +1390,7 @@ int yh_q_overlap_indexed(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_ov
     // (k_reduce_replicas reads every replica of both sets: 16 -> 8 replicas took 4 us off the step, with no
     // measurable change of the lookup kernel at 1.3e5 hits per sample)
     static const u32 ri_env = [] { const char* e = yh_tune_env("YH_INDEX_REPS"); return e ? (u32)atoi(e) : 0u; }();
-    // tiles of IDX_THREADS x U hashes once there are enough of them for every CU (k_index_lookup_tile)
+    // tiles of 1024 x U hashes once there are enough of them for every CU (k_index_lookup_tile; the shapes: yh_lookup.h)
     // (measured, 10^6-hash rotating samples with 1.6e5 hits: one hash per lane in 256-lane workgroups 38-40 us, tiles of U = 2
     // 35.7-36.3, U = 4 slower; no hits at all 32.5 / 31.5; an 83 k-hash sample 13 / 23)
     // YH_INDEX_TILE (debug gate): 256 = the small aggregating form, 1/2/4 = 1024-lane tiles of U
@@ -1443,8 +1398,8 @@ int yh_q_overlap_indexed(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_ov
     // (step time on the bench database, us, by sample size 1e5 / 2e5 / 3e5 / 4e5 / 5e5 / 7e5: small form 27.5 / 29.9 / 34.7 /
     // 37.9 / 40.5 / 43.5; 1024-lane tiles of one hash 29.3 / 30.0 / 33.5 / 33.7 / 36.4 / 41.7; of two 35.1 / 34.9 / 35.0 / 36.0 /
     // 36.9 / 41.1)
-    int U = n_sample >= 512ull * IDX_THREADS ? 2 : n_sample >= 256ull * IDX_THREADS ? 1 : 256;
-    if (tile_env == 1 || tile_env == 2 || tile_env == 4 || tile_env == 256) U = (int)tile_env;
+    const YhTileShape shape = tile_env == 256 ? yh_tile_shape(0) : tile_env == 1 ? yh_tile_shape(1) : tile_env == 2 ? yh_tile_shape(2)
+                              : tile_env == 4 ? yh_tile_shape(3) : yh_tile_shape_for(n_sample);
     // the aggregating forms leave one atomic per (workgroup, reference): four replicas are enough there (10^6-hash sample:
     // step 49.9 -> 48.4 us; two: 51.7; 83 k-hash real-shape sample: 28.8 / 26.3 / 25.4 us with 8 / 4 / 2)
     const u32 r_want = ri_env ? ri_env : 4u;
@@ -1457,18 +1412,16 @@ int yh_q_overlap_indexed(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_ov
     yh_ring_record_begin(db, db->ev_overlap);
     u8* const d_hitflags = (for_exclusive && db->n_shared && !fused) ? db->d_hit : nullptr;
     u32* const d_reps2 = fused ? reps2 : nullptr;
-    const u32* const d_filter = yh_filter_of(db);
-#define YH_TILE_LAUNCH(UU, TT, BB, FILTER)                                                                                        \
-    k_index_lookup_tile<UU, TT, BB><<<(u32)((n_sample + (u64)(TT) * (UU) - 1) / ((u64)(TT) * (UU))), TT, 0, st>>>(                 \
-        TileLookup{d_sample, n_sample, yh_dir_view(db), FILTER, db->filter_mul, db->d_po, db->d_pr, reps1, R - 1, N, d_hitflags,    \
-                   d_reps2, db->d_work_count, db->d_bad, db->bad_gen})
-    if (n_sample && db->n_distinct && U == 256)
-        // small samples: latency-bound, so no filter read in front of the bucket; 256-lane workgroups keep every CU busy
-        YH_TILE_LAUNCH(1, 256, 8, nullptr);
-    else if (n_sample && db->n_distinct && U == 4) YH_TILE_LAUNCH(4, IDX_THREADS, YH_IDX_TBITS, d_filter);
-    else if (n_sample && db->n_distinct && U == 2) YH_TILE_LAUNCH(2, IDX_THREADS, YH_IDX_TBITS, d_filter);
-    else if (n_sample && db->n_distinct && U == 1) YH_TILE_LAUNCH(1, IDX_THREADS, YH_IDX_TBITS, d_filter);
-#undef YH_TILE_LAUNCH
+    if (n_sample && db->n_distinct) {
+        const TileLookup q{d_sample, n_sample, yh_dir_view(db), shape.filter ? yh_filter_of(db) : nullptr, db->filter_mul, db->d_po, db->d_pr,
+                           reps1, R - 1, N, d_hitflags, d_reps2, db->d_work_count, db->d_bad, db->bad_gen};
+        switch (shape.form) {
+        case 0: k_index_lookup_tile<1, 256, 8><<<shape.tiles(n_sample), 256, 0, st>>>(q); break;
+        case 1: k_index_lookup_tile<1, 1024, 10><<<shape.tiles(n_sample), 1024, 0, st>>>(q); break;
+        case 2: k_index_lookup_tile<2, 1024, 10><<<shape.tiles(n_sample), 1024, 0, st>>>(q); break;
+        default: k_index_lookup_tile<4, 1024, 10><<<shape.tiles(n_sample), 1024, 0, st>>>(q); break;
+        }
+    }
     else if (fused && db->d_work_count)
         YH_HIP(hipMemsetAsync(db->d_work_count, 0, sizeof(u32), st));
     yh_ring_record_end(db, db->ev_overlap);
@@ -1502,10 +1455,10 @@ int yh_q_step_fused(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_overlap
     u32 R;
     YH_TRY(ensure_reps(db, R));
     while (R > 1 && R > 4u) R >>= 1;
-    // One geometry per launch: the sample's size picks it (as for the stand-alone lookup: 256-lane workgroups below 262 144
-    // hashes, 1024-lane tiles of one or two hashes per lane above); a draining launch takes the small one.
-    const int form = !d_sample ? 0 : n_sample >= 512ull * 1024 ? 2 : n_sample >= 256ull * 1024 ? 1 : 0;
-    const u32 threads = form ? 1024u : 256u, waves = threads / 64, tslots = form ? 1024u : 256u;
+    // One geometry per launch: the sample's size picks it (as for the stand-alone lookup: yh_tile_shape_for); a draining
+    // launch takes the small one.
+    const YhTileShape shape = d_sample ? yh_tile_shape_for(n_sample) : yh_tile_shape(0);
+    const u32 threads = shape.threads, waves = threads / 64, tslots = 1u << shape.tbits;
     StepFused s{};
     u32 lds_words = 3 * tslots;  // the lookup role's hit table
     if (db->pend_excl >= 0) {   // exclusive pass of the step reduced by the previous launch
@@ -1532,18 +1485,18 @@ int yh_q_step_fused(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_overlap
         c_new = (int)(db->pipe_k % 3);
         const int parity = (int)(db->pipe_k & 1);
         u32* const reps1 = db->d_reps + (u64)parity * 2 * db->reps_cap;
-        const u32 per_wg = threads * (form == 2 ? 2u : 1u);
-        // (the small form reads no presence filter: such a launch is latency-bound)
-        s.look = TileLookup{d_sample, n_sample, yh_dir_view(db), form ? yh_filter_of(db) : nullptr, db->filter_mul, db->d_po, db->d_pr,
+        s.look = TileLookup{d_sample, n_sample, yh_dir_view(db), shape.filter ? yh_filter_of(db) : nullptr, db->filter_mul, db->d_po, db->d_pr,
                             reps1, R - 1, N, nullptr, reps1 + db->reps_cap, db->ctx_count[c_new], nullptr, 0u};
-        s.look_wgs = (u32)((n_sample + per_wg - 1) / per_wg);
+        s.look_wgs = shape.tiles(n_sample);
     }
     const u32 total = s.excl_wgs + s.red_wgs + s.look_wgs;
     if (total) {
         if (d_sample) yh_ring_record_begin(db, db->ev_overlap);
-        if (form == 2) k_step_fused<2, 1024, 10><<<total, 1024, lds_words * sizeof(u32), st>>>(s);
-        else if (form == 1) k_step_fused<1, 1024, 10><<<total, 1024, lds_words * sizeof(u32), st>>>(s);
-        else k_step_fused<1, 256, 8><<<total, 256, lds_words * sizeof(u32), st>>>(s);
+        switch (shape.form) {
+        case 2: k_step_fused<2, 1024, 10><<<total, 1024, lds_words * sizeof(u32), st>>>(s); break;
+        case 1: k_step_fused<1, 1024, 10><<<total, 1024, lds_words * sizeof(u32), st>>>(s); break;
+        default: k_step_fused<1, 256, 8><<<total, 256, lds_words * sizeof(u32), st>>>(s); break;
+        }
         if (d_sample) yh_ring_record_end(db, db->ev_overlap);
         YH_HIP(hipGetLastError());
     }
