@@ -296,6 +296,8 @@ int yh_run_device_join(yh_db* db);
  *   yh_pairwise, yh_index_stats, yh_db_nshared_device        | yes                                   | yes
  *   yh_abund / yh_abund_device                               | yes (no step state is read or written) | yes
  *   yh_explain / yh_explain_device                           | yes (no step state is read or written) | yes
+ *   yh_explain_batch / yh_explain_batch_device,              | yes (no step state is read or written) | yes
+ *     yh_explain_members_rows_device                         |                                       |
  *   yh_db_set_stream                                         | yes (drains the old stream first)      | yes
  *   (*) the CURRENT context = the one named by the last yh_run_local*_device / yh_run_finish*_device call (0 at start).
  * Every query entry point first completes the pending stages of pipelined steps (yh_run_device_join) by itself.          */
@@ -449,6 +451,51 @@ int yh_explain_device(yh_db* db, const uint64_t* d_sample, const uint32_t* d_abu
                       const uint8_t* d_member /* [N] */, uint8_t* d_flags /* [n_sample] or NULL */, uint64_t* d_totals /* [8][2] */);
 int yh_explain(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_t n_sample,
                const uint8_t* member, uint8_t* flags, uint64_t* totals);
+
+/* ---- the same for a BLOCK of samples, each with its own call sets (additive in ABI 8) ----------------------------------------
+ * yh_explain_batch_device answers 1..YH_BATCH_MAX_SAMPLES samples in ONE lookup launch.  The samples are laid out as for
+ * yh_run_batch_device: d_samples holds them back to back (each strictly ascending), d_sample_offsets[n_samples + 1]
+ * delimits them, total_hashes = d_sample_offsets[n_samples]; d_abund runs in parallel to d_samples (NULL: every abund(h) = 1).
+ * total_hashes is the CALLER's copy of d_sample_offsets[n_samples] (the offsets are never read on the host), as for
+ * yh_run_batch_device: it only sizes the launch and decides the "no hashes" case.  The kernel walks the samples by the device
+ * offsets alone, so a larger total_hashes costs idle workgroups and a smaller one only time (workgroups loop over the
+ * tiles) -- except total_hashes == 0 with non-empty device offsets, which looks nothing up and leaves zero totals.  The offsets
+ * must ascend and stay inside d_samples, d_abund and d_flags: they are not checked.
+ * Sample s has its OWN member row d_members + s * N (bit 7 masked off).  Contract: for every sample s,
+ *   d_flags[off[s] .. off[s + 1])  and  d_totals[s][8][2]
+ * equal what yh_explain_device returns for that sample alone with member table d_members + s * N.  d_flags may be NULL: the
+ * totals only.  An empty database or total_hashes == 0: all n_samples * 16 totals are zero and no flag is written (every
+ * total is written by every call: nothing of an earlier, larger block survives in the first n_samples rows).  All outputs
+ * are integers and do not depend on arrival order.  A workgroup looks up a tile of YH_EXPLAIN_BATCH_TILE consecutive hashes
+ * of one sample.  Like yh_explain_device the pass reads no step context, batch slot or work list (interleaving table
+ * above: yes / yes), completes pending pipelined stages first, is enqueued on the handle's stream and does not sync the
+ * host.  n_samples == 0 or > YH_BATCH_MAX_SAMPLES: YH_ERR_INVALID_ARG.  YH_ERR_UNSUPPORTED as for yh_explain_device.
+ * yh_explain_batch is the synchronous host form: it checks bit 7 of all n_samples * N member bytes (YH_ERR_INVALID_ARG)
+ * and every sample's ordering (YH_ERR_UNSORTED), then uploads, runs and downloads; totals [n_samples][8][2], flags
+ * [sample_offsets[n_samples]] or NULL.
+ *
+ * yh_explain_members_rows_device makes the member rows of a block from its compact rows (yh_run_batch_rows_unpack_device)
+ * and the present bytes the presence test left beside them (yh_presence_rows_device): d_present is [n_sets][cap_rows], a slice
+ * of up to seven coverages of its d_present output.  It clears all n_samples * N bytes of d_members and then stores, for every
+ * row k < min(*d_n_rows, cap_rows),
+ *   d_members[row.sample * N + row.ref] = OR over c < n_sets of (d_present[c * cap_rows + k] != 0) << c.
+ * The compact rows name a (sample, reference) pair at most once: each row owns its byte.  A row with sample >= n_samples or
+ * ref >= N is skipped.  *d_n_rows is read on the device: no host sync.  n_sets outside 1..7 or n_samples outside
+ * 1..YH_BATCH_MAX_SAMPLES: YH_ERR_INVALID_ARG.  Enqueued on the handle's stream behind pending pipelined stages and a
+ * finish stream's rows; reads no handle state but N (interleaving table above: yes / yes).
+ * (No reference counterpart, as for yh_explain.)                                                                            */
+#ifndef YH_EXPLAIN_BATCH_TILE
+#define YH_EXPLAIN_BATCH_TILE 2048
+#endif
+int yh_explain_members_rows_device(yh_db* db, const yh_batch_row* d_rows, const uint32_t* d_n_rows, uint64_t cap_rows,
+                                   const uint8_t* d_present /* [n_sets][cap_rows] */, uint32_t n_sets /* 1..7 */,
+                                   uint32_t n_samples, uint8_t* d_members /* [n_samples][N] */);
+int yh_explain_batch_device(yh_db* db, const uint64_t* d_samples, const uint64_t* d_sample_offsets /* [n_samples + 1] */,
+                            const uint32_t* d_abund /* [total_hashes] or NULL: all 1 */, uint32_t n_samples, uint64_t total_hashes,
+                            const uint8_t* d_members /* [n_samples][N] */, uint8_t* d_flags /* [total_hashes] or NULL */,
+                            uint64_t* d_totals /* [n_samples][8][2] */);
+int yh_explain_batch(yh_db* db, const uint64_t* samples, const uint64_t* sample_offsets, const uint32_t* abund, uint32_t n_samples,
+                     const uint8_t* members, uint8_t* flags, uint64_t* totals);
 
 /* ---- the subset words of a block in compact form (ABI 5) ----------------------------------------------------------------
  * Between the two halves of a batched hash-range run every rank needs the OR of all ranks' subset words.  The dense row

@@ -12,7 +12,15 @@ yh_run_indexed_device.  HIP events on the handle's stream around `iters` back-to
 samples (so the buckets come from HBM, not from a cache warmed by the previous call), after a warm-up of every call; the
 calls alternate inside each of `rounds` rounds and the median round is reported with the spread.  Prints one JSON line and
 writes it to --out (default profiles/residual/bench_explain.json).  Also records what writing the residual signature of a
-10^6-hash sample costs on the host (residual.residual_signature + sigio.write_sig_zip)."""
+10^6-hash sample costs on the host (residual.residual_signature + sigio.write_sig_zip).
+
+    python scripts/bench_explain.py --batch [--batch-iters 10] [--commit ID] [--out FILE]
+
+The batched leg alone (default --out profiles/residual/bench_explain_batch.json): blocks of 256 real-shape samples and of 32
+10^6-hash samples, resident on the device as yh_run_batch_device takes them, each sample with the references it overlaps as
+call set 0 of its own member row.  Two ways to the same flags and totals are timed in the same process on the same block,
+alternating inside each round: (a) one yh_explain_batch_device, (b) a loop of yh_explain_device over the block's samples --
+existing code, the yardstick.  Both are checked against each other before anything is timed."""
 from __future__ import annotations
 
 import argparse
@@ -47,18 +55,111 @@ def write_cost(n_hashes: int) -> dict:
     return {"n_hashes": int(mins.size), "n_residual": len(res.minhash), "cut_s": round(t1 - t0, 4), "write_sig_zip_s": round(t2 - t1, 4)}
 
 
+def batch_leg(args) -> dict:
+    """(a) yh_explain_batch_device against (b) a loop of yh_explain_device over the same resident block, us per sample."""
+    import torch
+
+    dev = torch.device("cuda:0")
+    N = args.n_refs
+    values, offsets, _ = synth.config3_device(seed=1002, n_refs=N, n_sample=1000, device="cuda:0")
+    torch.cuda.synchronize()
+    db = RefDB.from_device(values.data_ptr(), offsets.data_ptr(), N)
+    stream = torch.cuda.Stream()
+    db.set_stream(stream.cuda_stream)
+    g = torch.Generator(device=dev)
+    g.manual_seed(6)
+    result = {"bench": "explain_batch", "commit": args.commit, "n_refs": N, "n_hashes_db": int(values.numel()),
+              "iters": args.batch_iters, "warmup": args.batch_warmup, "rounds": args.rounds, "tile": _lib.YH_EXPLAIN_BATCH_TILE,
+              "member_rows_bytes_per_sample": N, "shapes": {}}
+    for name, shape, n_sample, b in (("real_shape_83k_x256", "real", 83_000, 256), ("1e6_hash_x32", "present", 1_000_000, 32)):
+        samples = [synth.sample_device(values, offsets, seed=1900 + i, n_sample=n_sample, shape=shape) for i in range(b)]
+        offs = np.zeros(b + 1, dtype=np.int64)
+        offs[1:] = np.cumsum([int(s.numel()) for s in samples])
+        total = int(offs[-1])
+        d_samples = torch.cat(samples)
+        del samples
+        d_offs = torch.from_numpy(offs).to(dev)
+        d_abund = torch.randint(1, 1001, (total,), generator=g, device=dev, dtype=torch.int32)
+        counts = torch.zeros((3, b, N), dtype=torch.int32, device=dev)
+        db.run_batch_device(d_samples.data_ptr(), d_offs.data_ptr(), b, total, counts[0].data_ptr(), counts[1].data_ptr(), counts[2].data_ptr())
+        db.synchronize()
+        members = (counts[0] > 0).to(torch.uint8).contiguous()  # [b][N]: call set 0 of sample s = the references it overlaps
+        del counts
+        flags = [torch.zeros(total, dtype=torch.uint8, device=dev) for _ in range(2)]
+        totals = [torch.zeros((b, 16), dtype=torch.int64, device=dev) for _ in range(2)]
+        torch.cuda.synchronize()
+
+        def batched():
+            db.explain_batch_device(d_samples.data_ptr(), d_offs.data_ptr(), d_abund.data_ptr(), b, total, members.data_ptr(),
+                                    flags[0].data_ptr(), totals[0].data_ptr())
+
+        def looped():
+            for s in range(b):
+                o = int(offs[s])
+                db.explain_device(d_samples.data_ptr() + 8 * o, d_abund.data_ptr() + 4 * o, int(offs[s + 1]) - o,
+                                  members[s].data_ptr(), flags[1].data_ptr() + o, totals[1][s].data_ptr())
+
+        batched()
+        looped()
+        db.synchronize()
+        assert torch.equal(flags[0], flags[1]) and torch.equal(totals[0], totals[1]) and int(totals[0][:, 14].min()) > 0
+        assert bool((totals[0][:, 0] == totals[0][:, 14]).all())  # every known hash is explained by the overlapping references
+        calls = (("batched_us_per_sample", batched), ("looped_us_per_sample", looped))
+        times = {k: [] for k, _ in calls}
+        with torch.cuda.stream(stream):
+            for _k, fn in calls:
+                for _ in range(args.batch_warmup):
+                    fn()
+            db.synchronize()
+            for _ in range(args.rounds):
+                for k, fn in calls:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(stream)
+                    for _i in range(args.batch_iters):
+                        fn()
+                    e1.record(stream)
+                    e1.synchronize()
+                    times[k].append(e0.elapsed_time(e1) * 1e3 / args.batch_iters / b)
+        out = {"samples": b, "total_hashes": total, "hashes_in_database": int(totals[0][:, 14].sum()),
+               "references_overlapping_mean": round(float(members.sum()) / b, 1), "member_rows_bytes": b * N}
+        for k, v in times.items():
+            out[k] = round(float(np.median(v)), 2)
+            out[k.replace("_us_per_sample", "_rounds_us_per_sample")] = [round(x, 2) for x in v]
+            out[k.replace("_us_per_sample", "_spread_us_per_sample")] = round(max(v) - min(v), 2)
+        out["batched_over_looped"] = round(out["batched_us_per_sample"] / out["looped_us_per_sample"], 3)
+        out["batched_not_slower"] = bool(out["batched_us_per_sample"] <= out["looped_us_per_sample"])
+        result["shapes"][name] = out
+        del d_samples, d_abund, members, flags, totals
+        torch.cuda.empty_cache()
+    db.close()
+    return result
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", action="store_true", help="the batched leg alone (yh_explain_batch_device against a loop of yh_explain_device)")
+    ap.add_argument("--batch-iters", type=int, default=10)
+    ap.add_argument("--batch-warmup", type=int, default=3)
+    ap.add_argument("--commit", default="", help="recorded in the batched leg's output")
     ap.add_argument("--n-refs", type=int, default=85_205)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "residual",
-                                                  "bench_explain.json"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "residual",
+                                "bench_explain_batch.json" if args.batch else "bench_explain.json")
     import torch
 
     assert _lib.device_count() >= 1, "bench_explain.py needs an MI355X"
+    if args.batch:
+        line = json.dumps(batch_leg(args))
+        print(line)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+        return
     dev = torch.device("cuda:0")
     values, offsets, _ = synth.config3_device(seed=1002, n_refs=args.n_refs, n_sample=1000, device="cuda:0")
     torch.cuda.synchronize()

@@ -30,6 +30,7 @@ YH_RUN_SLOTS = 4
 YH_BATCH_SLOTS = 3
 YH_BATCH_MAX_SAMPLES = 256
 YH_PRESENCE_MAX_COVS = 16
+YH_EXPLAIN_BATCH_TILE = 2048
 YH_LOOKUP_AUTO, YH_LOOKUP_STREAM, YH_LOOKUP_INDEXED = 0, 1, 2
 
 _ERR_NAMES = {
@@ -152,6 +153,9 @@ SIGNATURES = {
     "yh_abund_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "yh_explain": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "yh_explain_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "yh_explain_members_rows_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_uint32, _vp]),
+    "yh_explain_batch_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp]),
+    "yh_explain_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "yh_host_alloc": (C.c_int, [C.POINTER(_vp), C.c_uint64]),
     "yh_host_free": (C.c_int, [_vp]),
     "yh_db_nshared_device": (C.c_int, [_vp, _vp]),

@@ -37,6 +37,7 @@ from .utils import logger
 
 BLOCK = _lib.YH_BATCH_MAX_SAMPLES  # samples per yh_run_batch_device
 MAX_COVS = _lib.YH_PRESENCE_MAX_COVS  # coverages per yh_presence_rows_device (more coverages take more launches)
+MAX_SETS = 7  # call sets per explain pass: bits 0..6 of a member byte (residual.MAX_SETS)
 SAMPLE_COLUMNS = ["stem", "path", "n_hashes", "mean_abundance", "n_overlapping", "status"]
 PRESENCE_COLUMNS = ["sample", "min_coverage", "organism_name", "num_matches", "acceptance_threshold_with_coverage", "p_vals"]
 PRESENCE_ABUNDANCE_COLUMNS = ["abund_median_exclusive", "relative_abundance"]  # behind them with --abundance
@@ -146,9 +147,12 @@ def _write_one(folder: str, results, covs, has_raw: bool, keep_raw: bool, show_a
 class _Device:
     """The device side of a cohort run: the block's buffers and the calls of one block."""
 
-    def __init__(self, db, covs, ksize: int, ani_thresh: float, thr_table: np.ndarray, cap: int = 0, abund_samples: int = 0):
+    def __init__(self, db, covs, ksize: int, ani_thresh: float, thr_table: np.ndarray, cap: int = 0, abund_samples: int = 0,
+                 residual_sets: int = 0):
         """cap: compact rows a block may have before it takes the dense rows (0: BLOCK * N, at most 2^20; grows after a
-        block that exceeded it).  abund_samples (--abundance): samples of the largest block; 0 = no abundance pass."""
+        block that exceeded it).  abund_samples (--abundance): samples of the largest block; 0 = no abundance pass.
+        residual_sets (--residual): the number of user coverages, the LAST residual_sets entries of covs, whose call sets
+        the block's explain passes answer, seven per pass; 0 = no explain pass."""
         import torch
 
         self.torch = torch
@@ -171,6 +175,16 @@ class _Device:
                           torch.zeros(shape, dtype=torch.float64, device=self.dev))
             self.abund_rows = None
             self.ev_abund = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        self.residual_sets = int(residual_sets)
+        if self.residual_sets > 0:  # per block: member rows [BLOCK][N], and per pass of seven call sets totals and flags
+            if self.residual_sets > self.covs.size:
+                raise ValueError(f"{self.residual_sets} call sets for {self.covs.size} coverages")
+            self.x_passes = (self.residual_sets + MAX_SETS - 1) // MAX_SETS
+            self.members = torch.zeros((BLOCK, max(N, 1)), dtype=torch.uint8, device=self.dev)
+            self.x_totals = torch.zeros((self.x_passes, BLOCK, 8, 2), dtype=torch.int64, device=self.dev)
+            self.x_flags = None  # [passes][the block's hashes], made per block
+            self.d_x_abund = None
+            self.ev_explain = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
 
     def _alloc(self, cap: int) -> None:
         t = self.torch
@@ -215,8 +229,22 @@ class _Device:
         ref = rows[:, 1].long().clamp_(0, w_ov.shape[1] - 1)
         return w_ov[smp, ref], w_m[smp, ref], med[smp, ref]
 
-    def launch(self, mins: List[np.ndarray], abunds=None) -> int:
+    def explain_pass(self, rows, d_n_rows: int, cap: int, out, b: int, total: int) -> None:
+        """The block's residual: per pass of up to seven user coverages, the samples' member rows from the rows' present
+        bytes (yh_explain_members_rows_device) and one yh_explain_batch_device over the uploaded block."""
+        first = self.covs.size - self.residual_sets  # (the forced 1.0 in front is no user coverage)
+        d_abund = self.d_x_abund.data_ptr() if self.d_x_abund is not None else 0
+        for p in range(self.x_passes):
+            c0 = first + p * MAX_SETS
+            self.db.explain_members_rows_device(rows.data_ptr(), d_n_rows, cap, out[1][c0].data_ptr(),
+                                                min(MAX_SETS, self.covs.size - c0), b, self.members.data_ptr())
+            self.db.explain_batch_device(self.d_samples.data_ptr(), self.d_offs.data_ptr(), d_abund, b, total,
+                                         self.members.data_ptr(), self.x_flags[p].data_ptr(), self.x_totals[p].data_ptr())
+
+    def launch(self, mins: List[np.ndarray], abunds=None, explain_abunds=None) -> int:
         """Queue one block: upload, batch counts, compact rows, presence test, row count to the host.  No host sync.
+        abunds (--abundance): every sample's abundances.  explain_abunds (the explain pass without --abundance): per sample
+        its abundances or None; a sample without counts every hash once.
         Events on the caller's (legacy default) stream, which the handle's blocking stream orders against, split the
         block's device time into upload, counts + compact rows, and the presence kernel."""
         t = self.torch
@@ -244,6 +272,20 @@ class _Device:
             self.ev_abund[0].record()
             self.abundance_pass(offs, b)
             self.ev_abund[1].record()
+        if self.residual_sets > 0:
+            total = int(offs[-1])
+            self.x_block = (b, total)
+            self.x_flags = t.empty((self.x_passes, max(total, 1)), dtype=t.uint8, device=self.dev)
+            self.d_x_abund = None
+            self.ev_explain[0].record()  # (the upload of a mixed cohort's abundances below belongs to the pass)
+            if abunds is not None:
+                self.d_x_abund = self.d_abund
+            elif explain_abunds is not None and total and any(a is not None for a in explain_abunds):
+                cat_ab = np.concatenate([np.ones(m.size, np.uint32) if a is None else np.ascontiguousarray(a, dtype=np.uint32)
+                                         for m, a in zip(mins, explain_abunds)]).view(np.int32)
+                self.d_x_abund = t.from_numpy(cat_ab).pin_memory().to(self.dev, non_blocking=True)
+            self.explain_pass(self.rows, self.n_rows[1].data_ptr(), self.cap, self.out, b, total)
+            self.ev_explain[1].record()
         self.n_rows_host.copy_(self.n_rows, non_blocking=True)
         return b
 
@@ -260,6 +302,8 @@ class _Device:
         timer["gpu_presence"] += ev[2].elapsed_time(ev[3]) / 1e3
         if self.abund is not None:
             timer["gpu_abund"] += self.ev_abund[0].elapsed_time(self.ev_abund[1]) / 1e3
+        if self.residual_sets > 0:
+            timer["gpu_explain"] += self.ev_explain[0].elapsed_time(self.ev_explain[1]) / 1e3
         k = int(self.n_rows_host[0])
         rows, out = self.rows, self.out
         abund_rows = self.abund_rows if self.abund is not None else None
@@ -277,11 +321,17 @@ class _Device:
             ev[2].record()
             if self.abund is not None:
                 abund_rows = self.gather_abundance(rows, b)
+            if self.residual_sets > 0:  # (the member rows came from the truncated rows: again from these)
+                self.ev_explain[0].record()
+                self.explain_pass(rows, d_k.data_ptr(), k, out, b, self.x_block[1])
+                self.ev_explain[1].record()
             t0 = time.perf_counter()
             t.cuda.synchronize(self.dev)
             timer["device_wait"] += time.perf_counter() - t0
             timer["gpu_counts"] += ev[0].elapsed_time(ev[1]) / 1e3
             timer["gpu_presence"] += ev[1].elapsed_time(ev[2]) / 1e3
+            if self.residual_sets > 0:
+                timer["gpu_explain"] += self.ev_explain[0].elapsed_time(self.ev_explain[1]) / 1e3
             timer["dense_fallback_blocks"] += 1
             self._alloc(int(k * 1.25) + 1)  # (the next blocks: compact rows again)
         t0 = time.perf_counter()
@@ -290,6 +340,8 @@ class _Device:
         if abund_rows is not None:
             got += ((abund_rows[0][:k].cpu().numpy().view(np.uint64), abund_rows[1][:k].cpu().numpy().view(np.uint64),
                      abund_rows[2][:k].cpu().numpy()),)
+        if self.residual_sets > 0:  # flags [passes][the block's hashes], totals [passes][b][8][2]
+            got += ((self.x_flags[:, :self.x_block[1]].cpu().numpy(), self.x_totals[:, :b].cpu().numpy().view(np.uint64)),)
         timer["d2h"] += time.perf_counter() - t0
         return got
 
@@ -300,8 +352,9 @@ def main(args, files: List[str]) -> dict:
     and the device buffers), parse_wait (the loop waiting for a block's sketches), device_wait (the loop waiting for a
     block's device work), gpu_h2d / gpu_counts / gpu_presence (device time of the uploads, the batch counts + compact rows,
     the presence kernel), gpu_abund (with --abundance: the block's yh_abund_device calls and the gather of their values at the
-    compact rows), gpu_explain (with --residual: the samples' host-form yh_explain calls, each of which uploads its sample
-    again and waits behind the device work of the next block), d2h, assemble, writes (what the write pool had left after the last block), cohort_files (the two
+    compact rows), gpu_explain (with --residual: device time of the block's member-row and batched explain passes, plus
+    the wall time of the host-form yh_explain calls of samples whose tables the host recomputed, or of every sample under
+    YACHT_COHORT_EXPLAIN=host), d2h, assemble, writes (what the write pool had left after the last block), cohort_files (the two
     cohort tables), total."""
     timer = {k: 0.0 for k in ("check", "db", "table", "device_setup", "parse_wait", "device_wait", "gpu_h2d", "gpu_counts",
                               "gpu_presence", "gpu_abund", "gpu_explain", "d2h", "assemble", "writes", "cohort_files", "dense_fallback_blocks", "total")}
@@ -338,7 +391,11 @@ def main(args, files: List[str]) -> dict:
         from . import residual
 
         residual_cov = residual.residual_coverage(args)
-    dev = _Device(db, covs, ksize, ani_thresh, t_thr, abund_samples=min(BLOCK, len(paths)) if want_abundance else 0)
+    # YACHT_COHORT_EXPLAIN=host: every sample's residual by its own host-form yh_explain call, as before the batched pass
+    # (A/B checks); otherwise only the samples whose tables the host recomputed below take it
+    device_explain = want_residual and os.environ.get("YACHT_COHORT_EXPLAIN") != "host"
+    dev = _Device(db, covs, ksize, ani_thresh, t_thr, abund_samples=min(BLOCK, len(paths)) if want_abundance else 0,
+                  residual_sets=len(user_covs) if device_explain else 0)
     timer["device_setup"] = time.perf_counter() - t0
 
     blocks = [list(range(i, min(i + BLOCK, len(paths)))) for i in range(0, len(paths), BLOCK)]
@@ -357,6 +414,10 @@ def main(args, files: List[str]) -> dict:
     def assemble(block, mins, got, abunds=None, sigs=None):
         rows, pv, pres, ncov = got[:4]
         t0 = time.perf_counter()
+        if device_explain:  # the block's flags [passes][hashes] and totals [passes][samples][8][2]
+            x_flags, x_totals = got[-1]
+            x_offs = np.zeros(len(block) + 1, dtype=np.int64)
+            x_offs[1:] = np.cumsum([m.size for m in mins])
         smp = rows[:, 0]
         order = np.argsort(smp, kind="stable")  # per sample, references ascending (the rows are in (reference, sample) order)
         bounds = np.searchsorted(smp[order], np.arange(len(block) + 1))
@@ -372,6 +433,7 @@ def main(args, files: List[str]) -> dict:
             e = rows[sel, 3].astype(np.int64)
             m = rows[sel, 4].astype(np.int64)
             cols = None
+            recomputed = False  # the dup_names branch below made this sample's tables on the host
             if want_abundance:  # the device's three values and the overlap count of the sample's rows
                 depth = [got[4][0][sel], got[4][1][sel], got[4][2][sel], rows[sel, 2]]
             if dup_names:  # get_exclusive_hashes selects by NAME: a reference without overlap may share a name with one that has it
@@ -388,6 +450,7 @@ def main(args, files: List[str]) -> dict:
                     e, m = ex_e[refs].astype(np.int64), ex_m[refs].astype(np.int64)
                     test = hr.hyp_test_native if os.environ.get("YACHT_HYP_NATIVE") == "1" else hr.hyp_test_batch
                     cols = [test(e, m, ksize, significance, ani_thresh, cov) for cov in covs]
+                    recomputed = True
             if cols is None:
                 cols = []
                 for c in range(len(covs)):
@@ -401,11 +464,15 @@ def main(args, files: List[str]) -> dict:
                 frames = [abundance.append_columns(f, *depth, total) for f in frames]
             frames = ry.trim_results(frames)
             explained = None
-            if want_residual:  # this sample's final presence calls are known: one host-form call (seven coverages each)
+            if want_residual:
                 call_sets = [refs[df["in_sample_est"].to_numpy().astype(bool)] for df in (frames if has_raw else frames[1:])]
-                t1 = time.perf_counter()
-                flags, totals = residual.explain_call_sets(db, mins[s], abunds[s] if abunds is not None else None, call_sets)
-                timer["gpu_explain"] += time.perf_counter() - t1
+                if device_explain and not recomputed:  # the device's present bytes ARE these call sets: the block's pass answered them
+                    flags = [x_flags[c // MAX_SETS, x_offs[s]:x_offs[s + 1]] for c in range(len(call_sets))]
+                    totals = [x_totals[c // MAX_SETS, s] for c in range(len(call_sets))]
+                else:  # the host's own tables: one host-form call per seven coverages
+                    t1 = time.perf_counter()
+                    flags, totals = residual.explain_call_sets(db, mins[s], abunds[s] if abunds is not None else None, call_sets)
+                    timer["gpu_explain"] += time.perf_counter() - t1
                 mh = sigs[s].minhash
                 total = n_hashes if mh.abundances is None else int(np.asarray(mh.abundances, dtype=np.uint64).sum(dtype=np.uint64))
                 row = residual.explained_frame(user_covs, [len(c) for c in call_sets], totals, n_hashes, total)
@@ -440,7 +507,7 @@ def main(args, files: List[str]) -> dict:
                 mins, abunds = [x[0] for x in mins], [x[1] for x in mins]
             timer["parse_wait"] += time.perf_counter() - t0
             parsing = parse(blocks[j + 1]) if j + 1 < len(blocks) else []
-            b = dev.launch(mins, abunds if want_abundance else None)
+            b = dev.launch(mins, abunds if want_abundance else None, abunds if device_explain and not want_abundance else None)
             if pending is not None:
                 assemble(*pending)  # (block j - 1 on the host while block j is on the device and block j + 1 is parsed)
             pending = (block, mins, dev.collect(b, timer), abunds, sigs)

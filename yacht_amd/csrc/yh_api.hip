@@ -1250,6 +1250,97 @@ int yh_explain(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_
     return rc;
 }
 
+// ---- the same for a block of samples, each with its own member row, and the member rows from a block's compact rows ----
+static bool explain_batch_samples_ok(uint32_t n_samples) {
+    if (n_samples >= 1 && n_samples <= YH_BATCH_MAX_SAMPLES) return true;
+    yh_set_error("1..%d samples per batch", YH_BATCH_MAX_SAMPLES);
+    return false;
+}
+
+int yh_explain_members_rows_device(yh_db* db, const yh_batch_row* d_rows, const uint32_t* d_n_rows, uint64_t cap_rows,
+                                   const uint8_t* d_present, uint32_t n_sets, uint32_t n_samples, uint8_t* d_members) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (n_sets < 1 || n_sets > 7) { yh_set_error("n_sets must be 1..7: the call sets are bits 0..6 of a member byte"); return YH_ERR_INVALID_ARG; }
+    if (!explain_batch_samples_ok(n_samples)) return YH_ERR_INVALID_ARG;
+    if (!d_n_rows || (db->n_refs && !d_members) || (cap_rows && (!d_rows || !d_present))) { yh_set_error("null device pointer"); return YH_ERR_INVALID_ARG; }
+    if (cap_rows > (1ull << 40)) { yh_set_error("cap_rows out of range"); return YH_ERR_INVALID_ARG; }
+    YH_TRY(db_select(db));
+    YH_TRY(pipe_join(db));
+    fin_join(db);  // (rows the rows pack / unpack wrote on the finish stream)
+    return yh_q_explain_members_rows(db, d_rows, d_n_rows, cap_rows, d_present, n_sets, n_samples, d_members);
+}
+
+int yh_explain_batch_device(yh_db* db, const uint64_t* d_samples, const uint64_t* d_sample_offsets, const uint32_t* d_abund,
+                            uint32_t n_samples, uint64_t total_hashes, const uint8_t* d_members, uint8_t* d_flags,
+                            uint64_t* d_totals) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (!explain_batch_samples_ok(n_samples)) return YH_ERR_INVALID_ARG;
+    if (!d_totals || !d_sample_offsets || (total_hashes && !d_samples) || (total_hashes && db->n_refs && !d_members)) {
+        yh_set_error("null device pointer");
+        return YH_ERR_INVALID_ARG;
+    }
+    YH_TRY(explain_supported(db));
+    YH_TRY(db_select(db));
+    YH_TRY(pipe_join(db));  // (no step context, batch slot or work list is read or written: nothing else to note)
+    return yh_q_explain_batch(db, (const u64*)d_samples, (const u64*)d_sample_offsets, d_abund, n_samples, total_hashes, d_members,
+                              d_flags, (u64*)d_totals);
+}
+
+int yh_explain_batch(yh_db* db, const uint64_t* samples, const uint64_t* sample_offsets, const uint32_t* abund, uint32_t n_samples,
+                     const uint8_t* members, uint8_t* flags, uint64_t* totals) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (!explain_batch_samples_ok(n_samples)) return YH_ERR_INVALID_ARG;
+    if (!sample_offsets || !totals) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+    const u64 total = sample_offsets[n_samples];
+    const u64 N = db->n_refs;
+    const u64 BN = (u64)n_samples * N;
+    if (sample_offsets[0] != 0 || (total && !samples) || (N && !members)) { yh_set_error("bad sample arrays or null member table"); return YH_ERR_INVALID_ARG; }
+    for (u64 j = 0; j < BN; ++j)
+        if (members[j] & 0x80u) {
+            yh_set_error("members[%llu][%llu] has bit 7 set: the call sets are bits 0..6, bit 7 of a flag means \"in the database\"",
+                         (u64)(j / N), (u64)(j % N));
+            return YH_ERR_INVALID_ARG;
+        }
+    for (uint32_t s = 0; s < n_samples; ++s) {
+        if (sample_offsets[s + 1] < sample_offsets[s] ||
+            yh_q_check_sorted_host((const u64*)samples + sample_offsets[s], sample_offsets[s + 1] - sample_offsets[s]) != YH_OK) {
+            yh_set_error("sample %u is not strictly ascending", s);
+            return YH_ERR_UNSORTED;
+        }
+    }
+    YH_TRY(explain_supported(db));
+    YH_TRY(db_select(db));
+    const bool looks_up = total && N && db->n_distinct;  // (otherwise: zero totals, no flags written)
+    u64 *d_s = nullptr, *d_o = nullptr;
+    u32* d_a = nullptr;
+    u8* d_bytes = nullptr;  // the totals, the member rows, the flags
+    const u64 off_members = (u64)n_samples * 16 * sizeof(u64), off_flags = off_members + ((BN + 15) & ~15ull);
+    int rc = YH_OK;
+    do {
+        if (yh_tmalloc(db, (void**)&d_s, std::max<u64>(total, 2) * sizeof(u64)) != hipSuccess ||
+            yh_tmalloc(db, (void**)&d_o, (u64)(n_samples + 1) * sizeof(u64)) != hipSuccess ||
+            (abund && yh_tmalloc(db, (void**)&d_a, std::max<u64>(total, 4) * sizeof(u32)) != hipSuccess) ||
+            yh_tmalloc(db, (void**)&d_bytes, off_flags + std::max<u64>(total, 16)) != hipSuccess) { yh_set_error("device allocation failed"); rc = YH_ERR_OOM; break; }
+        if ((total && hipMemcpyAsync(d_s, samples, total * sizeof(u64), hipMemcpyHostToDevice, db->stream) != hipSuccess) ||
+            hipMemcpyAsync(d_o, sample_offsets, (u64)(n_samples + 1) * sizeof(u64), hipMemcpyHostToDevice, db->stream) != hipSuccess ||
+            (abund && total && hipMemcpyAsync(d_a, abund, total * sizeof(u32), hipMemcpyHostToDevice, db->stream) != hipSuccess) ||
+            (BN && hipMemcpyAsync(d_bytes + off_members, members, BN, hipMemcpyHostToDevice, db->stream) != hipSuccess)) {
+            yh_set_error("explain upload failed"); rc = YH_ERR_HIP; break;
+        }
+        u8* const d_flags = flags ? d_bytes + off_flags : nullptr;
+        if ((rc = yh_explain_batch_device(db, (const uint64_t*)d_s, (const uint64_t*)d_o, abund ? d_a : nullptr, n_samples, total,
+                                          d_bytes + off_members, d_flags, (uint64_t*)d_bytes)) != YH_OK) break;
+        const bool down_ok = hipMemcpyAsync(totals, d_bytes, off_members, hipMemcpyDeviceToHost, db->stream) == hipSuccess &&
+                             (!flags || !looks_up || hipMemcpyAsync(flags, d_flags, total, hipMemcpyDeviceToHost, db->stream) == hipSuccess);
+        if (!down_ok || hipStreamSynchronize(db->stream) != hipSuccess) {
+            yh_set_error("explain download failed: %s", hipGetErrorString(hipGetLastError()));
+            rc = YH_ERR_HIP;
+        }
+    } while (0);
+    yh_tfree(db, d_s); yh_tfree(db, d_o); yh_tfree(db, d_a); yh_tfree(db, d_bytes);
+    return rc;
+}
+
 // ---- sharded run: the step in two halves around the exchange of the subset bits -----------------------
 int yh_db_set_ghosts(yh_db* db, uint64_t ghost_begin, uint64_t n_ghost, const uint32_t* d_ghost_src) {
     if (!db_ok(db)) return YH_ERR_INVALID_ARG;

@@ -104,6 +104,21 @@ def check_member(member, n_refs: int) -> np.ndarray:
     return np.ascontiguousarray(member, dtype=np.uint8)
 
 
+def check_members(members, n_samples: int, n_refs: int) -> np.ndarray:
+    """The member rows of RefDB.explain_batch as uint8 [n_samples, n_refs], or ValueError: 1..256 samples, one row per
+    sample, one byte per reference, each in [0, 127].  Host only: no library call."""
+    if not 1 <= int(n_samples) <= _lib.YH_BATCH_MAX_SAMPLES:
+        raise ValueError(f"a block holds 1..{_lib.YH_BATCH_MAX_SAMPLES} samples, not {int(n_samples)}")
+    members = np.asarray(members)
+    if members.ndim != 2 or members.shape != (int(n_samples), int(n_refs)):
+        raise ValueError(f"members must be [n_samples, n_refs] = [{int(n_samples)}, {int(n_refs)}], not {list(members.shape)}")
+    if members.size and members.dtype.kind not in "iub":
+        raise ValueError(f"member bytes must be integers, not {members.dtype}")
+    if members.size and (int(members.max()) > 0x7F or int(members.min()) < 0):
+        raise ValueError("member bytes must lie in [0, 127]: bit 7 must be clear, the call sets are bits 0..6")
+    return np.ascontiguousarray(members, dtype=np.uint8)
+
+
 class RefDB:
     """Reference sketches in HBM: delta stream, bucket table + presence filter, shared-hash inverted index."""
 
@@ -290,6 +305,44 @@ class RefDB:
         flags (0: none) and uint64 [8][2] totals out."""
         _lib.check(self._lib.yh_explain_device(self._h, C.c_void_p(d_sample), C.c_void_p(d_abund), n_sample, C.c_void_p(d_member),
                                                C.c_void_p(d_flags), C.c_void_p(d_totals)))
+
+    def explain_batch(self, samples: Sequence[np.ndarray], members, abunds=None, want_flags: bool = True):
+        """explain for a block of 1..256 samples, each with its own member row, in one lookup launch (yh_explain_batch).
+        members: uint8 [len(samples), n_refs], row s the member table of sample s.  abunds: None (all 1) or one entry per
+        sample, each an array of one abundance per hash or None (that sample's hashes count once).  Returns (flags, totals):
+        flags a list of uint8 arrays, one per sample (None with want_flags=False), totals uint64 [len(samples), 8, 2];
+        both equal explain's for each sample alone."""
+        b = len(samples)
+        members = check_members(members, b, self.n_refs)
+        samples = [_as_u64(s) for s in samples]
+        cat_ab = None
+        if abunds is not None:
+            if len(abunds) != b:
+                raise ValueError(f"{len(abunds)} abundance arrays for {b} samples")
+            if any(a is not None for a in abunds):
+                parts = [np.ones(s.size, dtype=np.uint32) if a is None else check_abundances(s, a)[1] for s, a in zip(samples, abunds)]
+                cat_ab = np.ascontiguousarray(np.concatenate(parts), dtype=np.uint32) if parts else None
+        values, offsets = pack_csr(samples)
+        flags = np.zeros(values.size, dtype=np.uint8) if want_flags else None
+        totals = np.zeros((b, 8, 2), dtype=np.uint64)
+        _lib.check(self._lib.yh_explain_batch(self._h, _ptr(values), _ptr(offsets), _ptr(cat_ab), b, _ptr(members), _ptr(flags),
+                                              _ptr(totals)))
+        return ([flags[int(offsets[s]):int(offsets[s + 1])] for s in range(b)] if want_flags else None), totals
+
+    def explain_batch_device(self, d_samples: int, d_offsets: int, d_abund: int, n_samples: int, total_hashes: int, d_members: int,
+                             d_flags: int, d_totals: int) -> None:
+        """yh_explain_batch_device: the block as for run_batch_device, uint32 abundances beside the hashes (0: all 1) and
+        uint8 [n_samples][N] member rows in, uint8 [total_hashes] flags (0: none) and uint64 [n_samples][8][2] totals out."""
+        _lib.check(self._lib.yh_explain_batch_device(self._h, C.c_void_p(d_samples), C.c_void_p(d_offsets), C.c_void_p(d_abund),
+                                                     n_samples, total_hashes, C.c_void_p(d_members), C.c_void_p(d_flags),
+                                                     C.c_void_p(d_totals)))
+
+    def explain_members_rows_device(self, d_rows: int, d_n_rows: int, cap_rows: int, d_present: int, n_sets: int, n_samples: int,
+                                    d_members: int) -> None:
+        """yh_explain_members_rows_device: the block's compact rows, their count (device) and uint8 [n_sets][cap_rows] present
+        bytes in, uint8 [n_samples][N] member rows out (cleared first)."""
+        _lib.check(self._lib.yh_explain_members_rows_device(self._h, C.c_void_p(d_rows), C.c_void_p(d_n_rows), cap_rows,
+                                                            C.c_void_p(d_present), n_sets, n_samples, C.c_void_p(d_members)))
 
     # sharded run (dist.ShardedRefDB): the step in two halves around the exchange of the subset bits
     def set_ghosts(self, ghost_begin: int, n_ghost: int, d_ghost_src: int) -> None:
