@@ -322,7 +322,11 @@ int yh_run_finish_device(yh_db* db, int ctx, const uint32_t* d_global_bits, uint
  *   yh_run_finish_range_device  global subset = OR of the n_ranks gathered rows (row r starts r * stride_words words
  *                               behind d_gathered_bits); d_n_excl = this rank's share of n_exclusive for it
  *   -- sum of the three rows over the ranks (one reduce per block of samples) --
- * Same step contexts and the same rule about other queries in between as the reference-sharded pair above.        */
+ * Same step contexts and the same rule about other queries in between as the reference-sharded pair above.
+ * A handle over N references WITHOUT A SINGLE HASH (a range that no reference reaches): yh_run_local_range_device returns
+ * YH_ERR_UNSUPPORTED and writes nothing -- there is no stream to look up; that rank's shares and bits are zero, and the
+ * caller writes them itself (yacht_amd/dist.py: HipRangeBackend) --, yh_run_finish_range_device returns YH_OK and leaves
+ * d_n_excl = 0 for all N references, whatever the other ranks' rows put into the subset.                            */
 int yh_run_local_range_device(yh_db* db, int ctx, const uint64_t* d_sample, uint64_t n_sample, uint32_t* d_overlap,
                               uint32_t* d_n_match, uint32_t* d_bits_out);
 int yh_run_finish_range_device(yh_db* db, int ctx, const uint32_t* d_gathered_bits, uint32_t n_ranks, uint64_t stride_words,
@@ -341,7 +345,9 @@ int yh_run_finish_range_device(yh_db* db, int ctx, const uint32_t* d_gathered_bi
  * wait there for the second): with several slots the subset words of block j travel while the lookups of block j + 1 run,
  * and block j - 1's compact rows are still being read (yacht_amd/dist.py: BatchRowsReducer keeps three blocks in flight).  A
  * second half without its first half in the slot, or with a different n_samples, or after yh_run_batch / yh_run_batch_device
- * ran meanwhile (they use slot 0), fails with YH_ERR_INVALID_ARG.                                                        */
+ * ran meanwhile (they use slot 0), fails with YH_ERR_INVALID_ARG.
+ * On a handle over N references without a single hash both halves return YH_OK: d_overlap, d_maskwords_out, d_n_excl and
+ * d_n_match are written and all zero, whatever the gathered words hold.                                                  */
 #define YH_BATCH_SLOTS 3
 int yh_run_batch_local_range_device(yh_db* db, int slot, const uint64_t* d_samples, const uint64_t* d_sample_offsets,
                                     uint32_t n_samples, uint64_t total_hashes, uint32_t* d_overlap, uint64_t* d_maskwords_out);
