@@ -65,11 +65,7 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "child":
         child()
     else:
-        # arguments: filter bits per distinct hash; "nt:2" = the same with lib/libyacht_hip_nt.so (a build_variant)
-        for arg in (sys.argv[1:] or ["0", "1", "2", "3", "4", "6"]):
-            variant, _, bph = arg.rpartition(":")
+        # arguments: filter bits per distinct hash
+        for bph in (sys.argv[1:] or ["0", "1", "2", "3", "4", "6"]):
             env = dict(os.environ, YH_FILTER_BPH=bph)
-            if variant:
-                env["YACHT_HIP_LIB"] = os.path.join(ROOT, "yacht_amd", "lib", f"libyacht_hip_{variant}.so")
-            print("variant", variant or "base", end=" ", flush=True)
             subprocess.run([sys.executable, os.path.abspath(__file__), "child"], env=env, check=False)

@@ -18,7 +18,7 @@ for r in rows[:30]:
     print(f"{nm:70s} {r['Calls']:>6s} {float(r['AverageNs'])/1e3:10.2f} {float(r['TotalDurationNs'])/1e6:9.3f} {100*float(r['TotalDurationNs'])/tot:6.1f}")
 PY
 cat gpurun_out/train_stats.txt
-# per-launch durations of k_pair_rows in launch order (tuning: YH_PAIR_PROBE=2 repeats the launch)
+# per-launch durations of k_pair_rows in launch order
 python3 - <<'PY'
 import csv, glob
 f = sorted(glob.glob("gpurun_out/prof_train/**/*kernel_trace.csv", recursive=True))

@@ -188,6 +188,64 @@ def test_distribution_sort_takes_uniform_keys_and_refuses_the_rest(hip_lib, heav
         assert not pieces and len(sorts) == 2 and all(ln.rstrip().endswith(verdict) for ln in sorts), verdicts
 
 
+GROUP_WORKER = r"""
+import json, sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from oracle import oracle
+from yacht_amd import synth
+from yacht_amd.engine import RefDB, YH_DB_PAIRWISE_ONLY
+
+n = int(sys.argv[2])
+rng = np.random.default_rng(40 + n)
+mh = synth.max_hash_for_scaled(1000)
+refs = [synth.random_sketch(rng, 50, mh) for _ in range(n)]
+extra = [[] for _ in range(n)]
+holders = (2, 3, 4, 5, 9, 33)         # inline records up to four holders, listed ones beyond
+for m in holders:
+    for _ in range(4):
+        h = int(rng.integers(1, mh))
+        for r in rng.choice(n, size=m, replace=False):
+            extra[int(r)].append(h)
+refs = [np.unique(np.concatenate([r, np.array(e, np.uint64)])) for r, e in zip(refs, extra)]
+values, offsets = synth.pack(refs)
+counts = np.unique(np.unique(values, return_counts=True)[1])
+ok, pairs = True, []
+for c in (0.0, 0.05):
+    wi, wj, wc, wstats = oracle.train_pairs(values, offsets, c, threads=4)
+    pairs.append(int(wi.size))
+    with RefDB(values, offsets, flags=YH_DB_PAIRWISE_ONLY) as db:
+        gi, gj, gc = db.pairwise(c)
+        ok = ok and bool(np.array_equal(gi, wi) and np.array_equal(gj, wj) and np.array_equal(gc, wc) and db.index_stats() == wstats)
+print(json.dumps({"ok": ok, "pairs": pairs, "H": int(values.size), "holders": [int(x) for x in counts]}))
+"""
+
+
+@pytest.mark.parametrize("n,path", [(40, "two_level"), (104, "pieces")])
+def test_both_grouping_kernels_at_neighbouring_small_sizes(hip_lib, n, path):
+    """The train handle's two grouping kernels, no tuning switch choosing between them.  40 sketches of ~50 hashes (at most
+    2 560 pairs: one bucket, so the piece geometry does not take it) go the two-level way and are grouped by k_bucket_group --
+    "[yh sort] ... fused: records of ... -> taken"; 104 sketches (more than 5 120 pairs: three buckets) take the piece
+    distribution and k_bucket_group5 -- "[yh pieces] ... -> taken".  Both hold hashes with 2, 3 and 4 holders (inline
+    records) and with 5, 9 and 33 (listed ones); pairs and statistics equal the oracle's, exactly."""
+    env = dict(os.environ)
+    env.update({"YH_DEBUG_TUNING": "1", "YH_TRACE_BUILD": "1", "YH_CHECK_SORT": "1"})
+    r = subprocess.run([sys.executable, "-c", GROUP_WORKER, ROOT, str(n)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out["H"] <= 2560 if path == "two_level" else out["H"] > 5120, out
+    assert out["holders"] == [1, 2, 3, 4, 5, 9, 33], out
+    # (at C = 0 one hash with 33 holders alone is 33 * 32 ordered pairs; the threshold 0.05 must cut some of them)
+    assert out["ok"] and out["pairs"][0] > 33 * 32 and 0 < out["pairs"][1] < out["pairs"][0], out
+    verdicts = [ln for ln in r.stderr.splitlines() if (ln.startswith("[yh sort]") or ln.startswith("[yh pieces]")) and " -> " in ln]
+    pieces = [ln for ln in verdicts if ln.startswith("[yh pieces]")]
+    sorts = [ln for ln in verdicts if ln.startswith("[yh sort]")]
+    if path == "two_level":  # (one handle per threshold)
+        assert not pieces and len(sorts) == 2 and all("fused: records of" in ln and ln.rstrip().endswith("taken") for ln in sorts), verdicts
+    else:
+        assert not sorts and len(pieces) == 2 and all("records of" in ln and ln.rstrip().endswith("taken") for ln in pieces), verdicts
+
+
 def test_tiny_sketches_and_shared_counts_on_the_train_handle(hip_lib):
     """6 000 sketches of 0..6 hashes drawn from a small pool (many share): every block of the position -> reference look-up
     of the fused path (one entry per 256 CSR positions) spans dozens of references, some of them empty.  Pairs, statistics and

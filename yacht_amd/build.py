@@ -65,8 +65,9 @@ def build_lib(force: bool = False, verbose: bool = False) -> str:
 
 
 def build_variant(name: str, defines: dict, verbose: bool = False) -> str:
-    """Tuning aid: build lib/libyacht_hip_<name>.so with -D overrides of the YH_* macros in
-    csrc/yh_common.h.  Select it at run time with YACHT_HIP_LIB=<path>."""
+    """Tuning aid: build lib/libyacht_hip_<name>.so with -D overrides of the numeric YH_* knobs, each an
+    `#ifndef` default next to the kernel it tunes (csrc/*.hip, csrc/yh_common.h).  Select it at run time
+    with YACHT_HIP_LIB=<path>."""
     os.makedirs(LIB_DIR, exist_ok=True)
     hipcc = _hipcc()
     out = os.path.join(LIB_DIR, f"libyacht_hip_{name}.so")

@@ -50,7 +50,7 @@ std::vector<std::pair<int, hipEvent_t>> g_cache_events;  // idle events, by devi
 uint64_t g_driver_allocs = 0;                         // hipMalloc calls made for handles (yh_alloc_stats)
 double g_driver_alloc_ms = 0.0;                       // host time inside them
 bool cache_on() {
-    static const bool on = [] { const char* off = yh_tune_env("YH_NO_POOL"); return !(off && off[0] == '1'); }();
+    static const bool on = !yh_tune_flag("YH_NO_POOL");
     return on;
 }
 hipEvent_t cache_event_take(int device) {  // (g_cache_mu held)
@@ -71,7 +71,7 @@ void cache_event_give(int device, hipEvent_t e) {  // (g_cache_mu held)
 }  // namespace
 // (YH_TRACE_BUILD=1 behind the tuning gate: every device allocation that took the host more than 0.5 ms, to stderr)
 static bool alloc_trace_on() {
-    static const bool on = [] { const char* e = yh_tune_env("YH_TRACE_BUILD"); return e && e[0] == '1'; }();
+    static const bool on = yh_tune_flag("YH_TRACE_BUILD");
     return on;
 }
 static double alloc_now_ms() {
@@ -275,8 +275,7 @@ static void ring_destroy(EventRing& r) {
 static int timing_every() {
     static int every = -1;
     if (every < 0) {
-        const char* e = yh_tune_env("YH_TIMING_EVERY");
-        every = e ? atoi(e) : 32;  // (an event pair costs the stream ~5 us: every 8th launch was 1.2 us of a 45 us step)
+        every = (int)yh_tune_int("YH_TIMING_EVERY", 32);  // (an event pair costs the stream ~5 us: every 8th launch was 1.2 us of a 45 us step)
         if (every < 0) every = 0;
     }
     return every;
@@ -288,7 +287,7 @@ std::mutex g_pin_mu;
 PinBuf g_pin[4];
 }
 void* yh_pin_acquire(u64 bytes) {
-    static const bool off = [] { const char* e = yh_tune_env("YH_NO_PIN"); return e && e[0] == '1'; }();  // (tests: the pageable paths)
+    static const bool off = yh_tune_flag("YH_NO_PIN");  // (tests: the pageable paths)
     if (off || bytes == 0 || bytes > ((u64)64 << 20)) return nullptr;
     std::lock_guard<std::mutex> lk(g_pin_mu);
     for (PinBuf& b : g_pin)
@@ -521,7 +520,7 @@ static int db_create_common(const u64* values, const u64* offsets, bool on_devic
             (void)hipStreamSynchronize(db->stream);  // (stream-ordered allocations: there before another stream copies into them)
             // a large host database goes up in chunks that are sorted and merged while the next one crosses the bus
             // (yh_build_upload_sorted); a small one in one piece
-            static const u64 chunk_min = [] { const char* e = yh_tune_env("YH_UPLOAD_CHUNK_MIN"); return e ? (u64)atoll(e) : (u64)12 << 20; }();
+            static const u64 chunk_min = (u64)yh_tune_int("YH_UPLOAD_CHUNK_MIN", 12ll << 20);
             chunked = pk ? true : (H >= chunk_min && n_refs >= 4);  // (a packed database always: yh_db_create_packed unpacks small ones on the host)
             const double t_up = alloc_now_ms();
             if (hipMemcpy(d_offsets_in, offsets, (n_refs + 1) * sizeof(u64), hipMemcpyHostToDevice) != hipSuccess ||
@@ -613,7 +612,7 @@ int yh_db_create_packed(const void* packed, uint64_t packed_bytes, int device_id
     try {  // (the view's and the host unpack's vectors are sized by the blob's header: no exception crosses the C boundary)
         YhPackedCsr v;
         YH_TRY(yh_csr_view(packed, packed_bytes, &v));
-        static const u64 chunk_min = [] { const char* e = yh_tune_env("YH_UPLOAD_CHUNK_MIN"); return e ? (u64)atoll(e) : (u64)12 << 20; }();
+        static const u64 chunk_min = (u64)yh_tune_int("YH_UPLOAD_CHUNK_MIN", 12ll << 20);
         if (!(v.n_hashes >= chunk_min && v.n_refs >= 4)) {
             std::vector<uint64_t> values(std::max<u64>(v.n_hashes, 1)), offsets(v.n_refs + 1);
             uint64_t h = 0, n = 0;
@@ -1631,7 +1630,7 @@ static int submit_common(yh_db* db, int slot, const void* sample, u64 n_or_bytes
     YH_TRY(slot_prepare(db, s, n_sample, packed_bytes, rows_staged));
     s.h_bad[0] = 0;
     s.h_bad[1] = 0;
-    static const bool one_up = [] { const char* e = yh_tune_env("YH_ONE_UPLOAD_STREAM"); return e && e[0] == '1'; }();
+    static const bool one_up = yh_tune_flag("YH_ONE_UPLOAD_STREAM");
     // (two engines only for the packed form: two raw 8 MB copies at once share the link and complete in bursts -- p90 0.35 ms)
     hipStream_t up = db->st_in[(packed && !one_up) ? (slot & 1) : 0];
     if (packed) {

@@ -95,15 +95,6 @@ __global__ void __launch_bounds__(256) k_batch_lookup(const u64* __restrict__ sa
         u32* row = overlap + (u64)s * n_refs;
         u32* row2 = ovsh + (u64)s * n_refs;
         auto add = [&](u32 ref, bool shared) {
-#if defined(YH_ABLATE_BATCH) && YH_ABLATE_BATCH  // timing-only build (build.py build_variant): no counting, results wrong
-            if (ref == 0x7ffffff1u) row[0] = 1;
-            return;
-#endif
-#if defined(YH_BATCH_DIRECT_ATOMICS) && YH_BATCH_DIRECT_ATOMICS  // measurement build: one global atomic per hit, no LDS table (results right)
-            atomicAdd(&row[ref], 1u);
-            if (shared) atomicAdd(&row2[ref], 1u);
-            return;
-#endif
             const int slot = yh_hit_slot<BATCH_TBITS>(tkey, ref);
             if (slot >= 0) {
                 atomicAdd(&tcnt[slot], 1u);
@@ -127,6 +118,10 @@ __global__ void __launch_bounds__(256) k_batch_lookup(const u64* __restrict__ sa
         // j + 1's presence word and round j + 2's sample hash requested behind round j's bucket, so that a round is one dependent
         // latency long instead of two: k_batch_lookup 3 622 -> 3 693 us per block of 256 samples at G = 1, 496 -> 512 at G = 8 --
         // nothing: with 32 resident waves per CU taking turns the pass is not waiting for its own chain.)
+        // (Measured and dropped, with builds that are in the history: ONE GLOBAL ATOMIC PER HIT instead of the LDS hit table -- 4.01 ms
+        // per block of 256 samples against 3.62 -- and NON-TEMPORAL LOADS of the buckets and of the sample hashes -- slower:
+        // profiles/r06/ablate_batch_reads.txt, profiles/r05/sweep_batch_nt.txt.  The first file has what the pass's reads cost: without
+        // the bucket reads 1.30 ms of 3.71, without the filter words 2.22.)
         // BATCH_U hashes of a lane at a time: all presence words are requested, then the buckets of the hashes that passed,
         // then they are looked at (BATCH_U = 1: word, bucket, counts, next hash)
         for (u64 k0 = i * BATCH_TILE; k0 < k_end; k0 += 256u * BATCH_U) {  // (workgroup-uniform)
@@ -136,36 +131,12 @@ __global__ void __launch_bounds__(256) k_batch_lookup(const u64* __restrict__ sa
 #pragma unroll
             for (int u = 0; u < BATCH_U; ++u) {
                 const u64 k = k0 + (u64)u * 256u + threadIdx.x;
-#if defined(YH_BATCH_NT) && (YH_BATCH_NT & 2)
-                h[u] = __builtin_nontemporal_load(&samples[off[s] + min(k, k_end - 1)]);
-#else
                 h[u] = samples[off[s] + min(k, k_end - 1)];
-#endif
                 ok[u] = k < k_end && h[u] <= dv.max_hash;
                 if (!ok[u]) h[u] = 0;  // (still a valid word / bucket to read)
             }
-#if defined(YH_ABLATE_BATCH_READS) && (YH_ABLATE_BATCH_READS & 2)  // timing-only build: no filter word is read (see below)
-            const u32* const probe_filter = nullptr;
-#else
-            const u32* const probe_filter = filter;
-#endif
-            yh_probe_filter<BATCH_U>(dv, probe_filter, filter_mul, h, ok);
-#if defined(YH_ABLATE_BATCH_READS) && (YH_ABLATE_BATCH_READS & 1)  // timing-only build: the filter word is read, no bucket is (results wrong)
-            if (probe_filter) {
-#pragma unroll
-                for (int u = 0; u < BATCH_U; ++u) ok[u] = ok[u] && h[u] == 0x123456789abcdefull;
-            }
-#endif
-#if defined(YH_ABLATE_BATCH_READS) && (YH_ABLATE_BATCH_READS & 2)  // timing-only build: the hashes that WOULD pass a
-            // perfect filter are not known, so every fourth hash reads its bucket (0.25 per hash: the bench samples' 0.27 + none of the 0.12 false positives)
-#pragma unroll
-            for (int u = 0; u < BATCH_U; ++u) ok[u] = ok[u] && ((h[u] >> 7) & 3ull) == 0;
-#endif
-#if defined(YH_BATCH_NT) && (YH_BATCH_NT & 1)
-            yh_probe_request<BATCH_U, true>(dv, h, ok, probe);
-#else
-            yh_probe_request<BATCH_U, false>(dv, h, ok, probe);
-#endif
+            yh_probe_filter<BATCH_U>(dv, filter, filter_mul, h, ok);
+            yh_probe_request<BATCH_U>(dv, h, ok, probe);
 #pragma unroll
             for (int u = 0; u < BATCH_U; ++u) hits_of(yh_probe_resolve<BATCH_U>(dv, h, ok, probe, u));
         }
@@ -643,7 +614,7 @@ int yh_q_run_batch(yh_db* db, const u64* d_samples, const u64* d_soff, u32 n_sam
     if (total_hashes && db->n_distinct) {
         const u64 n_tiles = (total_hashes + BATCH_TILE - 1) / BATCH_TILE + n_samples;  // (a ragged tile per sample)
         if (n_tiles >> 31) { yh_set_error("batch too large"); return YH_ERR_INVALID_ARG; }
-        static const long grid_env = [] { const char* e = yh_tune_env("YH_BATCH_GRID"); return e ? atol(e) : -1L; }();
+        static const long grid_env = (long)yh_tune_int("YH_BATCH_GRID", -1);
         // (workgroups of the launch, each looping over its slots: 2 048 -- the resident set -- 19.5 us per sample of a block of 256 at
         // rs214 scale, 4 096 16.5, 8 192 15.5, 16 384 14.8 (rounds 3-5), 32 768 14.2, one per slot 14.5: profiles/r06/sweep_batch_grid.txt)
         const u64 grid_cap = grid_env < 0 ? 32768ull : grid_env == 0 ? (u64)0x7fffff00 : (u64)grid_env;  // (0: one workgroup per slot)
@@ -678,7 +649,7 @@ int yh_q_run_batch(yh_db* db, const u64* d_samples, const u64* d_soff, u32 n_sam
         k_batch_sets<<<sets_blocks, 256, 0, st>>>(db->d_work, db->d_work_count, db->d_hrec, db->d_hrecx, db->d_hmult, db->d_pr,
                                                    d_maskword, N, d_excl, npl);
     }
-    static const bool dense_final = [] { const char* e = yh_tune_env("YH_BATCH_DENSE_FINAL"); return e && e[0] == '1'; }();
+    static const bool dense_final = yh_tune_flag("YH_BATCH_DENSE_FINAL");
     if (dense_final) {
         k_batch_final<<<grid_for(BN, 256, 8192), 256, 0, st>>>(n_samples, N, db->d_sizes, db->d_nshared, d_overlap, d_ovsh,
                                                                d_excl, d_match, d_gathered ? d_maskword : nullptr);

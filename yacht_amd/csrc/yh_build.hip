@@ -573,7 +573,7 @@ static double trace_now() {
     return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
 }
 static bool trace_on() {
-    static const bool on = [] { const char* e = yh_tune_env("YH_TRACE_BUILD"); return e && e[0] == '1'; }();
+    static const bool on = yh_tune_flag("YH_TRACE_BUILD");
     return on;
 }
 #define TRACE(label) do { if (trace_on()) { const double t__ = trace_now(); fprintf(stderr, "[yh build] %-28s +%.3f ms\n", label, t__ - t_prev); t_prev = t__; } } while (0)
@@ -586,7 +586,7 @@ static bool trace_on() {
 // and read again), k_idx_emit with its counting atomic per posting, k_pair_transpose with its isolated store per posting,
 // the posting arrays, and the host's prefix sum over nshared[] in yh_pairwise.
 static bool fz_wanted(const yh_db* db) {
-    static const bool off = [] { const char* e = yh_tune_env("YH_NO_FUSED_TRAIN"); return e && e[0] == '1'; }();
+    static const bool off = yh_tune_flag("YH_NO_FUSED_TRAIN");
     return !off && (db->flags & YH_DB_PAIRWISE_ONLY) && !(db->flags & YH_DB_NO_INDEX) && db->n_refs > 0 && db->n_hashes > 0;
 }
 static void fz_drop(yh_db* db) {
@@ -633,7 +633,7 @@ static int fz_finish(yh_db* db, yh_psort* ps, bool* took, bool* unsorted) {
 }
 
 // The same through the distribution WITHOUT a first level (yh_sort.hip: k_piece_bounds / k_piece_part): no position ->
-// reference table (the pairs bring their reference), the bounds pass clears the records.
+// reference table (the pairs bring their reference), and the grouping pass writes every position's record (none is cleared).
 static int fzp_begin(yh_db* db, const u64* d_offsets, u64 max_hash, yh_pieces** pc) {
     const u64 N = db->n_refs, H = db->n_hashes;
     *pc = nullptr;
@@ -885,7 +885,7 @@ static int upload_sorted_impl(yh_db* db, const u64* h_values, const u64* h_offse
     TRACE("sorted");
     if (rc == YH_OK && db->max_hash > max_last) { yh_set_error("internal: largest hash above the largest last element"); rc = YH_ERR_HIP; }
     if (rc == YH_OK && !fused) {
-        static const bool check = [] { const char* e = yh_tune_env("YH_CHECK_SORT"); return e && e[0] == '1'; }();
+        static const bool check = yh_tune_flag("YH_CHECK_SORT");
         if (check) {
             u32 bad = 0;
             UP_HIP(hipMemsetAsync(db->d_flag, 0, 4, st));
@@ -994,8 +994,8 @@ int yh_build_index(yh_db* db, const u64* d_values, const u64* d_offsets, u64* d_
 
     bool try_psort = yh_psort_applicable(H, db->max_hash);
     if (!d_sk_pre && try_psort && fz_wanted(db) && db->max_hash != ~0ull && yh_pc_applicable(H, db->max_hash, N)) {
-        // the fused path from device memory WITHOUT a first level: bounds pass (ordering check, records cleared), the
-        // distribution of the pieces, the grouping pass
+        // the fused path from device memory WITHOUT a first level: bounds pass (ordering check), the distribution of the
+        // pieces, the grouping pass (every position's record)
         yh_pieces* pc = nullptr;
         bool took = false, unsorted = false;
         YH_TRY(fzp_begin(db, d_offsets, db->max_hash, &pc));
@@ -1071,7 +1071,7 @@ int yh_build_index(yh_db* db, const u64* d_values, const u64* d_offsets, u64* d_
         // buckets that overflow go through a side list) --, rocPRIM's LSD radix sort -- stable: equal hashes keep ascending
         // references -- for anything else
         bool sorted = false;
-        static const bool no_pc_sort = [] { const char* e = yh_tune_env("YH_NO_PIECES_SORT"); return e && e[0] == '1'; }();
+        static const bool no_pc_sort = yh_tune_flag("YH_NO_PIECES_SORT");
         if (rc == YH_OK && try_psort && !no_pc_sort && db->max_hash != ~0ull && yh_pc_applicable(H, db->max_hash, N)) {
             bool unsorted = false;
             u64 sp_pairs = 0, sp_buckets = 0;
@@ -1122,7 +1122,7 @@ int yh_build_index(yh_db* db, const u64* d_values, const u64* d_offsets, u64* d_
             IDX_HIP(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, (const u64*)d_values, d_sk, ids_src, d_sv,
                                               (size_t)H, 0u, end_bit, st));
         }
-        static const bool check_sorted = [] { const char* e = yh_tune_env("YH_CHECK_SORT"); return e && e[0] == '1'; }();
+        static const bool check_sorted = yh_tune_flag("YH_CHECK_SORT");
         if (rc == YH_OK && check_sorted) {  // (tests / fuzzer: the order on the device, whichever sort made it)
             u32 bad = 0;
             IDX_HIP(hipMemsetAsync(db->d_flag, 0, 4, st));
@@ -1182,7 +1182,7 @@ int yh_build_index(yh_db* db, const u64* d_values, const u64* d_offsets, u64* d_
         IDX_HIP(hipMemsetAsync(db->d_g, 0, std::max<u64>(db->n_shared, 2) * sizeof(u64), st));
         // The bucket table over the distinct hashes (sample-driven lookups) is part of every handle that
         // answers sample queries, unless YH_DB_NO_DIRECTORY / YH_NO_DIRECTORY=1 opts out.
-        static const bool dir_env_off = [] { const char* e = yh_tune_env("YH_NO_DIRECTORY"); return e && e[0] == '1'; }();
+        static const bool dir_env_off = yh_tune_flag("YH_NO_DIRECTORY");
         const bool full = !(db->flags & (YH_DB_NO_DIRECTORY | YH_DB_PAIRWISE_ONLY)) && !dir_env_off && db->n_distinct > 0;
         unsigned bits = 1;
         while (bits < 64 && (db->max_hash >> bits) != 0) ++bits;
@@ -1197,7 +1197,7 @@ int yh_build_index(yh_db* db, const u64* d_values, const u64* d_offsets, u64* d_
             return (u64)std::min<unsigned __int128>(m, ~(u64)0);
         };
         const u64 mul_c = mul_for(nb_c);
-        static const bool wide_env = [] { const char* e = yh_tune_env("YH_WIDE_BUCKETS"); return e && e[0] == '1'; }();
+        static const bool wide_env = yh_tune_flag("YH_WIDE_BUCKETS");
         // a bucket spans ceil(2^bits / mul) hash values: the low 32 bits identify a hash inside it iff that is <= 2^32
         const bool compact = full && !wide_env && nb_c <= 0xfffffff0ull && mul_c > 0 &&
                              (bits <= 32 || (((unsigned __int128)1 << bits) + mul_c - 1) / mul_c <= ((unsigned __int128)1 << 32));
@@ -1270,10 +1270,10 @@ int yh_build_index(yh_db* db, const u64* d_values, const u64* d_offsets, u64* d_
             // Presence filter in front of the buckets (k_index_lookup_tile): one bit per 1 / YH_FILTER_BPH of a hash's
             // share of the range, indexed monotonically like the buckets, so that a sorted sample walks it front to back.
             // A sample hash whose bit is clear is not in the database and its bucket is never read.
-            static const u32 fbph = [] { const char* e = yh_tune_env("YH_FILTER_BPH"); return e ? (u32)atoi(e) : 4u; }();
+            static const u32 fbph = (u32)yh_tune_int("YH_FILTER_BPH", 4);
             // (below ~10^6 distinct hashes the whole table is cache resident and the filter only adds a dependent read;
             // YH_FILTER_MIN lowers the bar for tests)
-            static const u64 fmin = [] { const char* e = yh_tune_env("YH_FILTER_MIN"); return e ? (u64)atoll(e) : (u64)(1u << 20); }();
+            static const u64 fmin = (u64)yh_tune_int("YH_FILTER_MIN", 1 << 20);
             if (rc == YH_OK && fbph && db->n_distinct >= fmin) {
                 const u64 fbits = ((db->n_distinct * fbph + 511) / 512) * 512;
                 db->filter_mul = mul_for(fbits);

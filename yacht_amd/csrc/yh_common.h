@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string>
 #include <vector>
 
@@ -40,6 +41,9 @@ void yh_set_error(const char* fmt, ...);
 // YH_DEBUG_TUNING=1: one gate, so that a production process never changes behaviour because of a stray variable.
 // Returns the variable's value, or nullptr (gate closed or variable unset).
 const char* yh_tune_env(const char* name);
+// the two usual parses: a switch ("1" = on) and an integer with a default
+inline bool yh_tune_flag(const char* name) { const char* e = yh_tune_env(name); return e && e[0] == '1'; }
+inline long long yh_tune_int(const char* name, long long dflt) { const char* e = yh_tune_env(name); return e ? atoll(e) : dflt; }
 
 constexpr int STREAM_BLOCK = 1024;          // elements per block of the delta stream = 16 per lane
 constexpr u32 STREAM_NONE = 0xffffffffu;
@@ -386,15 +390,6 @@ struct YhDirView {
         // measured 3-10 us SLOWER per launch: profiles/r03/filter_sweep.txt)
         a = p[0]; b = p[1]; c = p[2]; d = p[3];
     }
-    // the same with non-temporal loads: the bucket is read once and should not push re-used lines (the presence filter of a
-    // batched pass) out of the XCD's L2
-    __device__ __forceinline__ void cbkt_request_nt(u64 h, v4u& a, v4u& b, v4u& c, v4u& d) const {
-        const v4u* p = reinterpret_cast<const v4u*>(cbkt) + 4 * yh_bucket_of(h, bkt_lsh, bkt_mul);
-        a = __builtin_nontemporal_load(p);
-        b = __builtin_nontemporal_load(p + 1);
-        c = __builtin_nontemporal_load(p + 2);
-        d = __builtin_nontemporal_load(p + 3);
-    }
     // ... and look at them
     __device__ __forceinline__ u32 cbkt_resolve(u64 h, const v4u a, const v4u b, const v4u c, const v4u d) const {
         const u32 lo = (u32)h, n = b.w & 0xfu;
@@ -464,7 +459,7 @@ int yh_q_pairwise(yh_db* db, double c_thresh, u64 r0, u64 r1);
 int yh_q_fz_nshared(yh_db* db);  // (yh_pairwise.hip) d_nshared of a fused handle, counted on first use
 // the presence filter a lookup may read in front of the compact buckets (null: none, or YH_NO_FILTER=1)
 inline const u32* yh_filter_of(const yh_db* db) {
-    static const bool filter_off = [] { const char* e = yh_tune_env("YH_NO_FILTER"); return e && e[0] == '1'; }();
+    static const bool filter_off = yh_tune_flag("YH_NO_FILTER");
     return (db->d_cbkt && db->d_filter && db->filter_mul && !filter_off) ? db->d_filter : nullptr;
 }
 int yh_q_check_sorted_host(const u64* v, u64 n);

@@ -66,18 +66,13 @@ __device__ __forceinline__ void yh_probe_filter(const YhDirView& dv, const u32* 
 // asm is a fence: all four loads of every bucket are issued, unconditionally, before anything looks at them.  Left to
 // itself the compiler sinks the loads of w[0] / w[8] under "entries > 0", which it only knows after the first loads
 // have come back -- a second dependent memory round trip per lookup (55 us instead of 30 for 10^6 lookups).
-// NT: non-temporal loads (a measurement build of the batched pass; slower for the single-sample lookup:
-// YhDirView::cbkt_request).
-template <int U, bool NT = false>
+template <int U>
 __device__ __forceinline__ void yh_probe_request(const YhDirView& dv, const u64 (&h)[U], const bool (&ok)[U], YhProbe<U>& p) {
     if (!dv.cbkt) return;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         p.a[u] = p.b[u] = p.c[u] = p.d[u] = YhDirView::v4u{0u, 0u, 0u, 0u};
-        if (ok[u]) {
-            if (NT) dv.cbkt_request_nt(h[u], p.a[u], p.b[u], p.c[u], p.d[u]);
-            else dv.cbkt_request(h[u], p.a[u], p.b[u], p.c[u], p.d[u]);
-        }
+        if (ok[u]) dv.cbkt_request(h[u], p.a[u], p.b[u], p.c[u], p.d[u]);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) asm volatile("" : "+v"(p.a[u]), "+v"(p.b[u]), "+v"(p.c[u]), "+v"(p.d[u]));

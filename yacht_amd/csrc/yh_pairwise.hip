@@ -110,9 +110,6 @@ constexpr u32 PAIR_SLOTS = 4;
 #endif
 constexpr int PAIR_U = YH_PAIR_U;  // records a lane has in flight
 
-#ifndef YH_ABLATE_PAIR
-#define YH_ABLATE_PAIR 0  // timing-only builds (results wrong): 1 no record pass, 2 no row clear / survivor scan, 4 records read but not added, 8 records read but not decoded
-#endif
 // FUSED: the records are yh_db::d_fz_rec's (8 bytes per CSR position, written by the sort's last pass: yh_sort.hip) and a
 // row is the extent of the reference's sketch -- entries of hashes nobody else holds are 0 and add nothing.
 template <bool FUSED> struct PairRec { typedef uint4 T; };
@@ -165,15 +162,13 @@ __global__ void __launch_bounds__(THREADS) k_pair_rows(const PairRows p) {
         rec[u] = recs[min(t, t1 - 1)];  // (unconditional, masked below: a load under `if` is waited for on the spot)
         if (t >= t1) mask_off(rec[u]);
     }
-    if (!(YH_ABLATE_PAIR & 2))
-        for (u32 j = tid; j < (HALF ? (w + 1u) >> 1 : w); j += THREADS) row[j] = 0;
+    for (u32 j = tid; j < (HALF ? (w + 1u) >> 1 : w); j += THREADS) row[j] = 0;
     __syncthreads();
     // (Same-address LDS adds are not what the pass waits for: counting a lane's first four columns in registers and
     // adding them once made it slower; without any add it is 15 % shorter.)
     auto addc = [&](u32 cc) {  // cc: a compact id
         const u32 c = cc - c0;
         if (c >= w) return;
-        if (YH_ABLATE_PAIR & 4) { if (c == 0x12345u) row[0] = 1; return; }
         if constexpr (HALF) atomicAdd(&row[c >> 1], 1u << ((c & 1u) * 16u));
         else atomicAdd(&row[c], 1u);
     };
@@ -230,7 +225,7 @@ __global__ void __launch_bounds__(THREADS) k_pair_rows(const PairRows p) {
         }
     };
     u32 nq = 0;  // descriptors in this wave's queue (wave-uniform)
-    for (u32 tb = t0; tb < ((YH_ABLATE_PAIR & 1) ? t0 : t1); tb += PAIR_U * THREADS) {  // (workgroup-uniform bounds: the ballot below)
+    for (u32 tb = t0; tb < t1; tb += PAIR_U * THREADS) {  // (workgroup-uniform bounds: the ballot below)
         Rec cur[PAIR_U];
 #pragma unroll
         for (int u = 0; u < PAIR_U; ++u) {
@@ -241,10 +236,6 @@ __global__ void __launch_bounds__(THREADS) k_pair_rows(const PairRows p) {
         }
 #pragma unroll
         for (int u = 0; u < PAIR_U; ++u) {
-            if constexpr (FUSED && (YH_ABLATE_PAIR & 8) != 0) {  // (timing only: the records read, nothing decoded)
-                if (cur[u] == 0x123456789abcull) row[0] = 1;
-                continue;
-            }
             bool is_list;
             u64 lq0 = 0;   // a list: its first entry in pr[] ...
             u32 lm = 0;    // ... and its length (this reference included)
@@ -301,7 +292,7 @@ __global__ void __launch_bounds__(THREADS) k_pair_rows(const PairRows p) {
     const u32 per = ((w + WAVES * 64u - 1) / (WAVES * 64u)) * 64u;
     const u32 jb = min(w, wid * per), je = min(w, jb + per);
     u32 mine = 0;
-    for (u32 j0 = jb; j0 < ((YH_ABLATE_PAIR & 2) ? jb : je); j0 += 64u) {
+    for (u32 j0 = jb; j0 < je; j0 += 64u) {
         const u32 j = j0 + lane;
         const u32 cnt = j < je ? count_of(j) : 0u;  // (rows are sparse: rid / sizes only behind a count)
         const bool keep = cnt != 0 && pair_keep(cnt, (u32)a, FUSED ? c0 + j : p.rid[c0 + j], p.sizes, p.c_relaxed);
@@ -609,7 +600,7 @@ int yh_q_pairwise(yh_db* db, double c_thresh, u64 r0, u64 r1) {
     // columns per row block: what the LDS holds
     typedef void (*RowsKernel)(const PairRows);
     // 16-bit counts (k_pair_rows<.., HALF>): a fused handle that knows its sketch sizes and has none above 65 535 hashes
-    static const bool no_half = [] { const char* e = yh_tune_env("YH_PAIR_NO_HALF"); return e && e[0] == '1'; }();
+    static const bool no_half = yh_tune_flag("YH_PAIR_NO_HALF");
     const bool half = fz && !no_half && db->h_sizes.size() == N && db->max_ref_size <= 0xffffu;
     // Lanes per row and columns per block go by what a CU can hold: a row block's LDS is its columns (2 or 4 bytes each), and the
     // WAVES resident per CU -- not the lanes of one row -- decide how well the phases of different rows overlap.  A row block is
@@ -619,7 +610,7 @@ int yh_q_pairwise(yh_db* db, double c_thresh, u64 r0, u64 r1) {
     // three blocks of 28 416 columns, 1 024 lanes: 4.8 ms (512 lanes: 6.1); two blocks of 73 728 -- one per CU --: 19.9 / 10.8 /
     // 7.1 ms at 256 / 512 / 1 024 lanes; round 4's 32-bit rows in three blocks of 36 864, 512 lanes: 11.5
     // (profiles/r05/rs214_rows_sweep.txt, sweep_pair_half.txt).
-    static const int threads_env = [] { const char* e = yh_tune_env("YH_PAIR_THREADS"); const int t = e ? atoi(e) : 0; return (t == 1024 || t == 512 || t == 256) ? t : 0; }();
+    static const int threads_env = [] { const int t = (int)yh_tune_int("YH_PAIR_THREADS", 0); return (t == 1024 || t == 512 || t == 256) ? t : 0; }();
     const u32 bytes_per_col = half ? 2u : 4u;
     static const bool big_lds = [] {
         bool ok = true;

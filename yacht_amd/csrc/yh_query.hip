@@ -410,6 +410,7 @@ struct Pending {  // one requested confirmation per lane
     u64 sv = 0;
 };
 #ifndef YH_ABLATE_STREAM
+// (kept: scripts/make_traffic_json.py derives the stream kernel's committed hbm_bytes_per_launch from these builds' counters)
 #define YH_ABLATE_STREAM 0  // traffic-attribution builds (results wrong): 1 = candidates are not confirmed (no srec / sample read), 2 = the probes do not read their lane's delta bytes again
 #endif
 __device__ __forceinline__ void pending_request(const StreamHit& hit, Pending& p, u64 pos, u32 sidx) {
@@ -871,32 +872,16 @@ __device__ __forceinline__ void lookup_tile_body(u32 wg, u32* tkey, u32* tcnt, u
         ok[u] = t < n && h[u] <= dv.max_hash;
         if (!ok[u]) h[u] = 0;  // (still a valid bucket to read)
     }
-#if !(defined(YH_ABLATE_LOOKUP) && (YH_ABLATE_LOOKUP & 32))
     // (the verdict of the sample's ordering check is asked for BEHIND the sample's own loads: in front of them every workgroup began
     // with a dependent round trip -- profiles/r05/ablate_step.txt: 0.2 us of the step)
     if (q.bad && *q.bad == q.bad_gen) return;
-#endif
     for (u32 k = threadIdx.x; k < TSLOTS; k += THREADS) { tkey[k] = 0; tcnt[k] = 0; tcnt2[k] = 0; }
     YhProbe<U> probe;
     u32 r[U];
-#if defined(YH_ABLATE_LOOKUP) && (YH_ABLATE_LOOKUP & 16)  // timing-only build: no presence filter read
-    yh_probe_filter<U>(dv, nullptr, q.filter_mul, h, ok);
-#else
     yh_probe_filter<U>(dv, filter, q.filter_mul, h, ok);
-#endif
-#if defined(YH_ABLATE_LOOKUP) && (YH_ABLATE_LOOKUP & 8)  // timing-only build: no bucket is read (every hash "absent" behind the filter)
-    if (dv.cbkt) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) ok[u] = ok[u] && h[u] == 0x123456789abcdefull;
-    }
-#endif
     yh_probe_request<U>(dv, h, ok, probe);
     __syncthreads();  // the table is clear
     auto add = [&](u32 ref, bool shared) {
-#if defined(YH_ABLATE_LOOKUP) && (YH_ABLATE_LOOKUP & 4)  // timing-only build: hits are not counted
-        if (ref == 0x7ffffff1u) my[0] = 1;
-        return;
-#endif
         const int slot = yh_hit_slot<TBITS>(tkey, ref);
         if (slot >= 0) {
             atomicAdd(&tcnt[slot], 1u);
@@ -915,16 +900,10 @@ __device__ __forceinline__ void lookup_tile_body(u32 wg, u32* tkey, u32* tcnt, u
         } else {
             const u32 gi = r[u] & 0x7fffffffu;
             if (q.hit) q.hit[gi] = 1;
-#if !(defined(YH_ABLATE_LOOKUP) && (YH_ABLATE_LOOKUP & 1))  // timing-only builds (build.py build_variant): results are wrong
             walk_holders(q.po, q.pr, gi, [&](u32 holder) { add(holder, true); });
-#endif
         }
     }
     __syncthreads();
-#if defined(YH_ABLATE_LOOKUP) && (YH_ABLATE_LOOKUP & 2)
-    if (n == 1) return;  // (never true: keeps the table alive)
-    return;
-#endif
     for (u32 k = threadIdx.x; k < TSLOTS; k += THREADS)
         if (tkey[k]) {
             count_add(&my[tkey[k] - 1], tcnt[k]);
@@ -1138,9 +1117,6 @@ __global__ void __launch_bounds__(THREADS, THREADS == 1024 ? 8 : 4) k_step_fused
     extern __shared__ u32 smem[];
     constexpr u32 TSLOTS = 1u << TBITS;
     u32 b = blockIdx.x;
-#if defined(YH_ABLATE_LOOKUP) && (YH_ABLATE_LOOKUP & 64)  // timing-only build: the launch's exclusive and reducer roles do nothing
-    if (b < s.excl_wgs + s.red_wgs) return;
-#endif
     if (b < s.excl_wgs) {
         if (s.excl_lds) excl_pieces_body<true, 2>(b, s.excl_wgs, smem, s.excl);
         else excl_pieces_body<false, 2>(b, s.excl_wgs, smem, s.excl);
@@ -1254,7 +1230,7 @@ static int yh_q_overlap_stream(yh_db* db, const u64* d_sample, u64 n_sample, u32
     const u64 nblk = db->slen / STREAM_BLOCK;
     // (a workgroup's set-up is two wave searches and a few KB of LDS: two blocks are enough to pay for it)
     // 512 workgroups = the two resident ones of each of the 256 CUs, one round (YH_STREAM_WGS: tests force one)
-    static const u32 wgs_env = [] { const char* e = yh_tune_env("YH_STREAM_WGS"); return (e && atoi(e) > 0) ? (u32)atoi(e) : 512u; }();
+    static const u32 wgs_env = [] { const long long v = yh_tune_int("YH_STREAM_WGS", 512); return v > 0 ? (u32)v : 512u; }();
     u32 wgs = (u32)std::min<u64>(wgs_env, std::max<u64>(nblk / 2, 1));
     if (db->wg_key_n != wgs) {  // the first t of every workgroup's block range: once per handle
         YH_HIP(hipStreamSynchronize(st));
@@ -1266,7 +1242,7 @@ static int yh_q_overlap_stream(yh_db* db, const u64* d_sample, u64 n_sample, u32
     u32 R;
     YH_TRY(ensure_reps(db, R));
     // hits leave a workgroup pre-summed (one atomic per workgroup and reference), so few replicas do
-    static const u32 r_env = [] { const char* e = yh_tune_env("YH_STREAM_REPS"); return e ? (u32)atoi(e) : (YH_XCD_ATOMICS ? 8u : 4u); }();
+    static const u32 r_env = (u32)yh_tune_int("YH_STREAM_REPS", YH_XCD_ATOMICS ? 8 : 4);
     while (R > 1 && R > r_env) R >>= 1;
     const bool fused = d_fused_excl != nullptr;
     const bool flags_too = flag_shared && db->has_index && !fused;
@@ -1317,7 +1293,7 @@ int yh_q_overlap(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_overlap, b
 // Returns 1 when this handle cannot take the fused path (the caller then runs the general one).
 int yh_q_run_fused(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_overlap, u32* d_excl, u32* d_match, int phases,
                    u32* d_bits_out, const u32* d_global_bits, bool use_indexed) {
-    static const bool off = [] { const char* e = yh_tune_env("YH_NO_FUSED_RUN"); return e && e[0] == '1'; }();
+    static const bool off = yh_tune_flag("YH_NO_FUSED_RUN");
     if (!db->d_sdelta || !db->has_index || db->n_refs == 0 || db->n_hashes == 0 ||
         (db->n_postings && (!db->d_hrec || !db->d_hpo || !db->d_work)) || n_sample > 0xfffffff0ull)
         return 1;
@@ -1353,7 +1329,7 @@ int yh_q_run_fused(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_overlap,
 }
 
 static bool fused_possible(const yh_db* db, const u32* d_fused_excl, bool for_exclusive) {
-    static const bool fused_off = [] { const char* e = yh_tune_env("YH_NO_FUSED_RUN"); return e && e[0] == '1'; }();
+    static const bool fused_off = yh_tune_flag("YH_NO_FUSED_RUN");
     return d_fused_excl && for_exclusive && db->d_work && db->d_hrec && db->d_hpo && !fused_off;
 }
 
@@ -1389,12 +1365,12 @@ int yh_q_overlap_indexed(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_ov
     YH_TRY(ensure_reps(db, R));
     // (k_reduce_replicas reads every replica of both sets: 16 -> 8 replicas took 4 us off the step, with no
     // measurable change of the lookup kernel at 1.3e5 hits per sample)
-    static const u32 ri_env = [] { const char* e = yh_tune_env("YH_INDEX_REPS"); return e ? (u32)atoi(e) : 0u; }();
+    static const u32 ri_env = (u32)yh_tune_int("YH_INDEX_REPS", 0);
     // tiles of 1024 x U hashes once there are enough of them for every CU (k_index_lookup_tile; the shapes: yh_lookup.h)
     // (measured, 10^6-hash rotating samples with 1.6e5 hits: one hash per lane in 256-lane workgroups 38-40 us, tiles of U = 2
     // 35.7-36.3, U = 4 slower; no hits at all 32.5 / 31.5; an 83 k-hash sample 13 / 23)
     // YH_INDEX_TILE (debug gate): 256 = the small aggregating form, 1/2/4 = 1024-lane tiles of U
-    static const long tile_env = [] { const char* e = yh_tune_env("YH_INDEX_TILE"); return e ? atol(e) : -1L; }();
+    static const long tile_env = (long)yh_tune_int("YH_INDEX_TILE", -1);
     // (step time on the bench database, us, by sample size 1e5 / 2e5 / 3e5 / 4e5 / 5e5 / 7e5: small form 27.5 / 29.9 / 34.7 /
     // 37.9 / 40.5 / 43.5; 1024-lane tiles of one hash 29.3 / 30.0 / 33.5 / 33.7 / 36.4 / 41.7; of two 35.1 / 34.9 / 35.0 / 36.0 /
     // 36.9 / 41.1)

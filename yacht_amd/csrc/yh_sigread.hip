@@ -436,7 +436,7 @@ struct Deflate {
     int (*raw)(void*, const void*, size_t, void*, size_t, size_t*) = nullptr;
     uint32_t (*crc)(uint32_t, const void*, size_t) = nullptr;
     Deflate() {
-        static const bool off = [] { const char* e = yh_tune_env("YH_NO_LIBDEFLATE"); return e && e[0] == '1'; }();
+        static const bool off = yh_tune_flag("YH_NO_LIBDEFLATE");
         if (off) return;
         void* h = dlopen("libdeflate.so.0", RTLD_NOW | RTLD_LOCAL);
         if (!h) return;
@@ -717,7 +717,7 @@ static int zip_sig_ingest_impl(const char* zip_path, const char* out_dir, int ks
     std::atomic<bool> oom{false};
     std::atomic<int> io_failed{0};
     // (YH_TRACE_BUILD=1 behind the tuning gate: where the threads' time went, summed over the threads)
-    static const bool trace = [] { const char* e = yh_tune_env("YH_TRACE_BUILD"); return e && e[0] == '1'; }();
+    static const bool trace = yh_tune_flag("YH_TRACE_BUILD");
     std::atomic<uint64_t> ns_read{0}, ns_gunzip{0}, ns_parse{0}, ns_write{0};
     auto now_ns = [] { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec; };
     const uint64_t t_begin = now_ns();

@@ -292,7 +292,7 @@ static_assert(RL_WIN % (SK_THREADS * SK_ITEMS) == 0, "one alignment for both ker
 static int launch_sketch(const u8* d_seq, u64 n_bytes, u32 k, u64 seed, u64 max_hash, u64 cap, u64* d_out, u64* d_cnt, hipStream_t st,
                          u64 win0, u64 win_end) {
     if (win_end <= win0) return YH_OK;
-    static const bool bytes_only = [] { const char* e = yh_tune_env("YH_SKETCH_BYTES"); return e && e[0] == '1'; }();
+    static const bool bytes_only = yh_tune_flag("YH_SKETCH_BYTES");
     const bool roll = k <= 64 && !bytes_only && (reinterpret_cast<uintptr_t>(d_seq) & 15u) == 0;
     const u64 per_block = roll ? (u64)RL_WIN : (u64)SK_THREADS * SK_ITEMS;
     const u64 blocks = (win_end - win0 + per_block - 1) / per_block;

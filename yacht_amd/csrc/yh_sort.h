@@ -36,7 +36,7 @@ int yh_psort_finish_emit(yh_db* db, yh_psort* s, u64* d_rec, u64 n_refs, u64 tot
 // ---- the same without a first level (round 5): regions are read in place as contiguous PIECES of the ascending sketches ----
 struct yh_pieces;
 bool yh_pc_applicable(u64 H, u64 max_hash, u64 n_refs);
-// d_rec: the H records of the pairwise pass (cleared by the bounds pass on its way through)
+// d_rec: the H records of the pairwise pass (not cleared: the grouping pass writes every position's record)
 int yh_pc_begin(yh_db* db, u64 H, u64 max_hash, u64 n_refs, u64* d_rec, yh_pieces** out);
 // the bounds pass over the sketches [r0, r1) holding n_pairs hashes (the chunks of an upload as they arrive); check_order:
 // flag sketches that are not strictly ascending

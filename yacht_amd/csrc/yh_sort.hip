@@ -24,10 +24,13 @@
 // chunk crosses PCIe, and only levels two and three remain behind the last byte (yh_build_upload_sorted).
 //
 // POSITION MODE (`yacht train`'s handle, yh_db::fz): the value of a pair is its CSR position, not its reference -- the
-// order is the same -- and the last pass (k_bucket_group) does not sort or write pairs at all: it groups the bucket's pairs
-// by hash in an LDS hash table and stores, at the position of every element whose hash another reference holds too,
-// the 8-byte record the pairwise pass reads ("the other holders").  No posting arrays, no rank per posting, no
-// transposition: see yh_build.hip (fz_*) and yh_pairwise.hip (k_pair_rows<.., true>).
+// order is the same -- and the last pass does not sort or write pairs at all: it groups the bucket's pairs by hash in an
+// LDS hash table and stores, at the position of every element whose hash another reference holds too, the 8-byte record
+// the pairwise pass reads ("the other holders").  No posting arrays, no rank per posting, no transposition: see
+// yh_build.hip (fz_*) and yh_pairwise.hip (k_pair_rows<.., true>).  Two grouping kernels, one per distribution:
+// k_bucket_group5 behind the piece distribution (k_piece_bounds, k_piece_part: packed pairs, every position's record
+// written), k_bucket_group behind the two-level one (k_part: databases too small for pieces; the first level clears the
+// records, the kernel writes those of shared hashes).
 #include "yh_common.h"
 #include "yh_sort.h"
 
@@ -56,15 +59,15 @@ constexpr u32 PART_MAX_BINS = 1024;  // bins per level (LDS histogram)
 #endif
 constexpr u32 BKT_SLOT_BITS = YH_BKT_BITS;
 constexpr u32 BKT_CAP = 1u << BKT_SLOT_BITS;   // pairs a final bucket may hold
-#ifndef YH_GROUP_NT
-#define YH_GROUP_NT 1  // 1: k_bucket_group5 reads its pairs with non-temporal loads (adopted); 2: k_piece_part stores them so (measured worse)
-#endif
 #ifndef YH_BKT_FILL8
 #define YH_BKT_FILL8 5   // eighths of its capacity a bucket holds on average (tuning: scripts/sweep_fill.sh)
 #endif
 constexpr u32 BKT_FILL = BKT_CAP / 8 * YH_BKT_FILL8;  // ... and holds on average (2 560 of 4 096; uniform keys: sd ~51; clustered references ~3x that)
 constexpr u32 BKT_THREADS = YH_BKT_THREADS;
 constexpr u32 BKT_ITEMS = BKT_CAP / BKT_THREADS;
+#ifndef YH_GROUP_SPEC_ITEMS
+#define YH_GROUP_SPEC_ITEMS (BKT_ITEMS / 2)  // pairs per thread k_bucket_group5 requests before it knows the bucket's count (tuning: scripts/sweep_fill.sh)
+#endif
 constexpr u32 BKT_SLOTS = BKT_CAP;   // fine slots of the counting sort inside a bucket (= 1 << BKT_SLOT_BITS)
 constexpr u32 TOT_LANES = 256;       // rows of the grouping pass's counters (k_bucket_group)
 constexpr u32 SLOT_MAX = 1024;       // pairs of one slot a pair ranks itself against (a hash held by that many references: 10^6 LDS reads); more: not this sort's input
@@ -367,13 +370,11 @@ struct BucketArgs {
     unsigned long long* totals;  // [TOT_LANES][8] {distinct hashes, shared hashes, their pairs, pairs seen, ...}: bucket b adds into row b % TOT_LANES
                                  // (one row of four counters for all 19 600 workgroups: 78 000 atomics on ONE cache line, ~6 ns each --
                                  // the whole 0.5 ms of this kernel at configs[3], whatever else it did: profiles/r05/ablate_group.txt)
-    u64 stride_v;                // packed pairs: elements between two buckets of in_v / list (in_k: cap_in)
+    u64 stride_v;                // k_bucket_group5: elements between two buckets of in_v / list (in_k: cap_in)
     u32* over_bits;              // != NULL: a bucket with more pairs than its capacity (k_bucket_sort: or with a crowded slot) is not an
                                  // error: its bit is set, flags[2] counts it, and its pairs are grouped / sorted from a side list
-    u32 rem_bits;                // != 0: PACKED pairs (k_piece_part): in_k = low rem_bits bits of the hash | reference << rem_bits
+    u32 rem_bits;                // k_bucket_group5's PACKED pairs (k_piece_part): in_k = low rem_bits bits of the hash | reference << rem_bits
                                  // (inside a bucket the hashes span less than 2^rem_bits: the low bits identify them), in_v = position
-    u32 write_all;               // k_bucket_group5: EVERY pair stores the record of its position (0: nobody else holds its hash) --
-                                 // the records are not cleared in front of the distribution (round 6)
 };
 
 // exclusive scan of arr[0 .. ITEMS * blockDim.x) in place, ITEMS consecutive words per thread; two barriers (the second one
@@ -574,17 +575,8 @@ __global__ void __launch_bounds__(BKT_THREADS) k_bucket_group(const BucketArgs a
     const u32 tid = threadIdx.x;
     const u64 b = (u64)(blockIdx.x & 7u) * a.per_xcd + (blockIdx.x >> 3);
     if ((blockIdx.x >> 3) >= a.per_xcd || b >= a.nb) return;
-    const u64 sv = a.stride_v ? a.stride_v : a.cap_in;
     u64 key[BKT_ITEMS];
     u32 val[BKT_ITEMS], rf[BKT_ITEMS], slot[BKT_ITEMS];
-#if defined(YH_GROUP_SPEC_LOADS) && YH_GROUP_SPEC_LOADS
-#pragma unroll
-    for (u32 k = 0; k < BKT_ITEMS; ++k) {
-        const u32 e = k * BKT_THREADS + tid;
-        key[k] = a.in_k[b * a.cap_in + e];
-        val[k] = a.in_v[b * sv + e];
-    }
-#endif
     if (a.cnt[b] > BKT_CAP && tid == 0) atomicOr(a.flags, 2u);
     const u32 n = min(a.cnt[b], BKT_CAP);
     if (n == 0) return;
@@ -592,21 +584,8 @@ __global__ void __launch_bounds__(BKT_THREADS) k_bucket_group(const BucketArgs a
     for (u32 k = 0; k < BKT_ITEMS; ++k) {
         const u32 e = k * BKT_THREADS + tid;
         slot[k] = NONE;
-#if defined(YH_ABLATE_GROUP) && (YH_ABLATE_GROUP & 16)  // timing-only build: not even the loads
-        if (e < n) { key[k] = b + e; val[k] = e; }
-#else
-#if !(defined(YH_GROUP_SPEC_LOADS) && YH_GROUP_SPEC_LOADS)  // (else: requested above, before the bucket's count was known)
-        if (e < n) { key[k] = a.in_k[b * a.cap_in + e]; val[k] = a.in_v[b * sv + e]; }
-#endif
-#endif
+        if (e < n) { key[k] = a.in_k[b * a.cap_in + e]; val[k] = a.in_v[b * a.cap_in + e]; }
     }
-#if defined(YH_ABLATE_GROUP) && (YH_ABLATE_GROUP & 8)  // timing-only build: the loads and nothing else
-    { u64 x = 0;
-#pragma unroll
-      for (u32 k = 0; k < BKT_ITEMS; ++k) if (k * BKT_THREADS + tid < n) x += key[k] + val[k];
-      if (x == 0x123456789abcdefull) a.rec[0] = x;
-      return; }
-#endif
     for (u32 i = tid; i < BKT_CAP / 2; i += BKT_THREADS) reinterpret_cast<uint4*>(tkey)[i] = make_uint4(0u, 0u, 0u, 0u);
     for (u32 i = tid; i < BKT_CAP / 4; i += BKT_THREADS) reinterpret_cast<uint4*>(thead)[i] = make_uint4(NONE, NONE, NONE, NONE);
     if (tid < 3) tot3[tid] = 0;
@@ -618,20 +597,10 @@ __global__ void __launch_bounds__(BKT_THREADS) k_bucket_group(const BucketArgs a
         const u32 e = k * BKT_THREADS + tid;
         bool won = false;
         if (e < n) {
-            u32 s;
-            if (a.rem_bits) {  // (uniform) the pair brings its reference; the table's key is the hash's low bits
-                rf[k] = (u32)(key[k] >> a.rem_bits);
-                key[k] &= (1ull << a.rem_bits) - 1ull;
-                s = (u32)((key[k] * 0x9E3779B97F4A7C15ull) >> (64 - BKT_SLOT_BITS));
-            } else {
-                rf[k] = ref_of(val[k], a.ref_tab, a.ref_off);
-                s = fine_of(key[k], a.lsh, a.mul_fine) & (BKT_CAP - 1u);
-            }
+            rf[k] = ref_of(val[k], a.ref_tab, a.ref_off);
+            u32 s = fine_of(key[k], a.lsh, a.mul_fine) & (BKT_CAP - 1u);
             eref[e] = rf[k];
             const unsigned long long k1 = key[k] + 1ull;  // (the fused path is taken only where the largest hash is below 2^64 - 1)
-#if defined(YH_ABLATE_GROUP) && (YH_ABLATE_GROUP & 4)  // timing-only build: no table inserts
-            won = (k1 & 1ull) != 0; tkey[s] = k1; slot[k] = s; enext[e] = 0xffffu; thead[s] = e;
-#else
             for (u32 probe = 0; probe < BKT_CAP; ++probe) {
                 const unsigned long long old = atomicCAS(reinterpret_cast<unsigned long long*>(&tkey[s]), 0ull, k1);
                 if (old == 0ull) { won = true; break; }
@@ -640,7 +609,6 @@ __global__ void __launch_bounds__(BKT_THREADS) k_bucket_group(const BucketArgs a
             }
             slot[k] = s;
             enext[e] = (u16)atomicExch(&thead[s], e);  // (NONE -> 0xffff)
-#endif
         }
         c0 += (u32)__popcll(__ballot(won));
     }
@@ -656,27 +624,19 @@ __global__ void __launch_bounds__(BKT_THREADS) k_bucket_group(const BucketArgs a
         if (slot[k] != NONE) {
             u32 others[3] = {0u, 0u, 0u};
             u32 cnt = 0, rank = 0;
-#if defined(YH_ABLATE_GROUP) && (YH_ABLATE_GROUP & 2)  // timing-only build: the chain is not walked
-            cnt = enext[e] != 0xffffu ? 1u : 0u; others[0] = eref[e ^ 1u];
-#else
             for (u32 j = thead[slot[k]]; j != 0xffffu && j != NONE; j = enext[j]) {
                 if (j == e) continue;
                 if (cnt < 3) others[cnt] = eref[j];
                 ++cnt;
                 rank += j < e ? 1u : 0u;
             }
-#endif
             const u32 len = cnt + 1u;
             first = enext[e] == 0xffffu;  // (the pair that claimed the chain: one per group)
             shared = len >= 2u;
             if (shared) {
                 if (len <= 4u && a.inline_ok) {
                     const u64 r = (u64)(others[0] + 1u) | (cnt > 1 ? (u64)(others[1] + 1u) << 21 : 0ull) | (cnt > 2 ? (u64)(others[2] + 1u) << 42 : 0ull);
-#if defined(YH_ABLATE_GROUP) && (YH_ABLATE_GROUP & 1)  // timing-only build: no record stores (results wrong)
-                    if (r == 0x123456789abcdefull) a.rec[val[k]] = r;
-#else
                     if (val[k] < a.n_pos) a.rec[val[k]] = r;
-#endif
                 } else {
                     glen[k] = len;
                     grank[k] = rank;
@@ -703,7 +663,7 @@ __global__ void __launch_bounds__(BKT_THREADS) k_bucket_group(const BucketArgs a
 #pragma unroll
     for (u32 k = 0; k < BKT_ITEMS; ++k)
         if (slot[k] != NONE && glen[k]) {
-            const u64 start = b * sv + thead[slot[k]];
+            const u64 start = b * a.cap_in + thead[slot[k]];
             a.list[start + grank[k]] = rf[k];
             if (val[k] < a.n_pos) a.rec[val[k]] = (1ull << 63) | ((u64)glen[k] << 40) | start;
         }
@@ -746,28 +706,15 @@ __global__ void __launch_bounds__(BKT_THREADS) k_bucket_group5(const BucketArgs 
     // slots beyond the count hold garbage nobody uses) -- a bucket holds ~2 560 pairs, so these are nearly all real --, the second
     // half behind the count, which has arrived meanwhile: only the pairs that exist.  (All four quarters up front: 0.96 GB read
     // for 0.60 GB of pairs at configs[3].)
-#if defined(YH_GROUP_SPEC_ALL) && YH_GROUP_SPEC_ALL
-    constexpr u32 SPEC_ITEMS = BKT_ITEMS;
-#elif defined(YH_GROUP_SPEC_ITEMS)
     constexpr u32 SPEC_ITEMS = YH_GROUP_SPEC_ITEMS;
-#else
-    constexpr u32 SPEC_ITEMS = BKT_ITEMS / 2;
-#endif
 #pragma unroll
     for (u32 k = 0; k < SPEC_ITEMS; ++k) {
         const u32 e = k * BKT_THREADS + tid;
-#if defined(YH_ABLATE_GROUP) && (YH_ABLATE_GROUP & 16)  // timing-only build: not even the loads
-        key[k] = (b * 0x9E3779B97F4A7C15ull + e * 0x7F4A7C15ull) >> 3; val[k] = e;
-#else
-#if YH_GROUP_NT & 1  // the bucket's pairs are read once: non-temporal, so that they do not push the record lines the XCD's L2 is
-        key[k] = __builtin_nontemporal_load(&a.in_k[b * a.cap_in + e]);   // collecting out before they are whole (round 6: the pass
-        // wrote 0.71 GB for 0.40 GB of records; with these 0.61 -- profiles/r06/sweep_group_nt.txt; the time is the same)
+        // the bucket's pairs are read once: non-temporal, so that they do not push the record lines the XCD's L2 is collecting
+        // out before they are whole (round 6: the pass wrote 0.71 GB for 0.40 GB of records; with these 0.61 --
+        // profiles/r06/sweep_group_nt.txt; the time is the same)
+        key[k] = __builtin_nontemporal_load(&a.in_k[b * a.cap_in + e]);
         val[k] = __builtin_nontemporal_load(&a.in_v[b * a.stride_v + e]);
-#else
-        key[k] = a.in_k[b * a.cap_in + e];
-        val[k] = a.in_v[b * a.stride_v + e];
-#endif
-#endif
     }
     for (u32 i = tid; i < BKT_CAP / 4; i += BKT_THREADS) reinterpret_cast<uint4*>(tidx)[i] = make_uint4(0u, 0u, 0u, 0u);
     if (tid < 3) tot3[tid] = 0;
@@ -785,11 +732,7 @@ __global__ void __launch_bounds__(BKT_THREADS) k_bucket_group5(const BucketArgs 
     for (u32 k = SPEC_ITEMS; k < BKT_ITEMS; ++k) {
         const u32 e = k * BKT_THREADS + tid;
         key[k] = 0; val[k] = 0;
-#if YH_GROUP_NT & 1
         if (e < n) { key[k] = __builtin_nontemporal_load(&a.in_k[b * a.cap_in + e]); val[k] = __builtin_nontemporal_load(&a.in_v[b * a.stride_v + e]); }
-#else
-        if (e < n) { key[k] = a.in_k[b * a.cap_in + e]; val[k] = a.in_v[b * a.stride_v + e]; }
-#endif
     }
 #pragma unroll
     for (u32 k = 0; k < BKT_ITEMS; ++k) {
@@ -811,21 +754,12 @@ __global__ void __launch_bounds__(BKT_THREADS) k_bucket_group5(const BucketArgs 
             const u64 rem = key[k] & rmask;
             const u64 mixed = rem * 0x9E3779B97F4A7C15ull;
             u32 s = (u32)(mixed >> (64 - BKT_SLOT_BITS));
-#if defined(YH_GROUP_LINEAR) && YH_GROUP_LINEAR
-            const u32 step = 1u;
-#else
             // DOUBLE HASHING: the probe step is a second (odd) function of the hash -- a wave makes max-over-lanes(probes) steps per
             // pair, and two hashes that collide do not share the rest of their probe sequences as they do with step 1 (simulated at
             // this load: 8.9 wave steps per four pairs against 11.6; the inserts are ~25 us per wave step at configs[3])
             const u32 step = ((u32)(mixed >> 20) & (BKT_CAP - 1u)) | 1u;
-#endif
             u32 rank = 0;
-#if defined(YH_ABLATE_GROUP) && (YH_ABLATE_GROUP & 4)  // timing-only build: no table inserts
-            tidx[s] = e + 1u; won = (rem & 1ull) != 0;
-            for (u32 probe = 0; probe < 0; ++probe) {
-#else
             for (u32 probe = 0; probe < BKT_CAP; ++probe) {
-#endif
                 const u32 old = atomicCAS(&tidx[s], 0u, e + 1u);
                 if (old == 0u) { won = true; break; }
                 if ((ekey[(old & 0xffffu) - 1u] & rmask) == rem) {  // this pair's hash: join
@@ -848,11 +782,7 @@ __global__ void __launch_bounds__(BKT_THREADS) k_bucket_group5(const BucketArgs 
         bool first = false, shared = false;
         if (st[k] != 0xffffffffu) {
             const u32 s = st[k] & 0xfffu, rank = st[k] >> 12;
-#if defined(YH_ABLATE_GROUP) && (YH_ABLATE_GROUP & 2)  // timing-only build: the slot is not read again
-            const u32 w = (u32)key[k] & 0x1ffffu;
-#else
             const u32 w = tidx[s];
-#endif
             const u32 members = w >> 16;
             first = rank == 0u;
             shared = members != 0u;
@@ -860,7 +790,7 @@ __global__ void __launch_bounds__(BKT_THREADS) k_bucket_group5(const BucketArgs 
             // pair of exactly one bucket, so the records need no clearing pass in front of the distribution (0.40 GB of zeros at
             // configs[3], written by k_piece_bounds until round 5), and a record line that this XCD's L2 collects from its buckets'
             // pairs now leaves it WHOLE (2.7e7 records scattered over 5e7 positions cost 1.9 x their bytes in partly written lines).
-            if (!shared && a.write_all && val[k] < a.n_pos) a.rec[val[k]] = 0ull;
+            if (!shared && val[k] < a.n_pos) a.rec[val[k]] = 0ull;
             if (shared) {
                 if (members <= 3u && a.inline_ok) {
                     // the other holders: the claimer (unless that is this pair) and the members but this one
@@ -872,18 +802,10 @@ __global__ void __launch_bounds__(BKT_THREADS) k_bucket_group5(const BucketArgs 
                     if (members > 1u && rank != 2u) o[cnt++] = m1;
                     if (members > 2u && rank != 3u) o[cnt++] = m2;
                     // (cnt = members: one of the up to four is this pair)
-#if defined(YH_ABLATE_GROUP) && (YH_ABLATE_GROUP & 2)
-                    u64 r = m0 + m1 + m2 + o[0] + 1;
-#else
                     u64 r = (u64)((u32)(ekey[o[0]] >> a.rem_bits) + 1u);
                     if (cnt > 1u) r |= (u64)((u32)(ekey[o[1]] >> a.rem_bits) + 1u) << 21;
                     if (cnt > 2u) r |= (u64)((u32)(ekey[o[2]] >> a.rem_bits) + 1u) << 42;
-#endif
-#if defined(YH_ABLATE_GROUP) && (YH_ABLATE_GROUP & 1)  // timing-only build: no record stores (results wrong)
-                    if (r == 0x123456789abcdefull) a.rec[val[k]] = r;
-#else
                     if (val[k] < a.n_pos) a.rec[val[k]] = r;
-#endif
                 } else {
                     listed |= 1u << k;
                     has_list = 1u;
@@ -931,8 +853,8 @@ __global__ void __launch_bounds__(BKT_THREADS) k_bucket_group5(const BucketArgs 
 // contiguous PIECE [bnd[r][i], bnd[r + 1][i]) of the CSR: region r does not have to be written out and read again (12 B
 // out + 12 B in per pair: k_part<1> 0.45-0.53 ms + the input side of k_part<2> at configs[3]) -- it can be READ IN PLACE.
 //   k_piece_bounds   one streaming pass over the CSR (a wave per sketch, 8-byte coalesced loads): where every region starts
-//                    in every sketch (transposed through LDS into region-major rows), the ordering check, and the clearing
-//                    of the pairwise records -- 8 B read + 8 B written per pair, nothing scattered
+//                    in every sketch (transposed through LDS into region-major rows) and the ordering check -- 8 B read per
+//                    pair, nothing scattered (until round 5 it also cleared the pairwise records: 8 B written per pair)
 //   k_piece_part     a tile = (region r, a group of S sketches): their pieces of r (~36 hashes = 288 contiguous bytes each at
 //                    configs[3]) are read straight from the CSR and distributed over the region's P2 buckets exactly as
 //                    k_part<2> does it (LDS histogram, one reserving atomic per (tile, bin), staged, coalesced runs) -- as
@@ -941,7 +863,7 @@ __global__ void __launch_bounds__(BKT_THREADS) k_bucket_group5(const BucketArgs 
 //                    position -> reference look-ups are gone), and the position.  Still 12 bytes.
 //                    All tiles of a region run on ONE XCD, consecutively (blockIdx % 8 = region % 8): the runs of a bucket
 //                    are completed in that XCD's L2 before they go to HBM.
-// Traffic per pair: 8 + 8 (bounds, clear) + 8 + 12 (distribution) against 8 + 12 + 8 and 12 + 12.
+// Traffic per pair: 8 (bounds) + 8 + 12 (distribution) against 8 + 12 + 8 and 12 + 12.
 constexpr u32 PC_MAX_S = 1023;   // sketches per tile (one thread each for the prefix of their piece lengths)
 #ifndef YH_PC_BOUND_THREADS
 #define YH_PC_BOUND_THREADS 512
@@ -965,7 +887,6 @@ struct PieceArgs {
     u64 mul;
     u32 lsh, rem_bits;
     u32 inv_p2;          // ceil(2^32 / P2): bucket / P2 = (bucket * inv_p2) >> 32 for every bucket < NB
-    u64* rec_clear;
     u64* out_a;          // [NB][stride_k] packed (hash remainder | reference << rem_bits)
     u32* out_p;          // [NB][stride_v] positions
     u64 stride_k, stride_v;  // elements between two buckets: BKT_CAP + a pad (see yh_pieces)
@@ -1012,7 +933,6 @@ __global__ void __launch_bounds__(PC_BOUND_THREADS) k_piece_bounds(const PieceAr
                 bool up_have = true;
                 if (lane == 0) { up_reg = carry_reg; up_h = carry_h; up_have = have; }
                 if (in) {
-                    if (a.rec_clear) a.rec_clear[p] = 0;
                     if (up_have && !(up_h < h[u])) bad = true;
                     // this element opens every region behind its predecessor's up to its own (none when the sketch is not
                     // ascending here: flagged above)
@@ -1088,11 +1008,7 @@ __global__ void __launch_bounds__(PART_THREADS) k_piece_part(const PieceArgs a) 
         }
 #pragma unroll
         for (u32 q = 0; q < PART_ITEMS; ++q)
-#if defined(YH_ABLATE_PART) && (YH_ABLATE_PART & 4)  // timing-only build: the pieces are not read (keys made up inside the region)
-            if (pos[q] != 0xffffffffu) key[q] = ((u64)r * a.P2 + (pos[q] * 2654435761u) % a.P2) * ((~0ull) / ((u64)a.P1 * a.P2 * 1000ull)) + pos[q];
-#else
             if (pos[q] != 0xffffffffu) key[q] = a.values[pos[q]];
-#endif
 #pragma unroll
         for (u32 q = 0; q < PART_ITEMS; ++q) {
             bin[q] = 0xffffffffu;
@@ -1123,11 +1039,7 @@ __global__ void __launch_bounds__(PART_THREADS) k_piece_part(const PieceArgs a) 
             if (b < a.P2) {
                 const u32 c = hist[b];
                 c_mine[q] = c;
-#if defined(YH_ABLATE_PART) && (YH_ABLATE_PART & 2)  // timing-only build: no reserving atomics (every tile writes at the bucket's start)
-                if (c) g_mine[q] = 0;
-#else
                 if (c) g_mine[q] = atomicAdd(&a.out_cnt[(u64)r * a.P2 + b], c);
-#endif
                 loc[b] = c;
             }
         }
@@ -1156,17 +1068,9 @@ __global__ void __launch_bounds__(PART_THREADS) k_piece_part(const PieceArgs a) 
                 if (at < BKT_CAP) {  // (a pair that finds its bucket full is dropped HERE: the bucket's count says so, the pass behind this
                     // one marks the bucket, and k_spill_collect fetches ALL its pairs from the sketches again -- the rare case pays)
                     const u64 bkt = (u64)r * a.P2 + b;
-#if defined(YH_ABLATE_PART) && (YH_ABLATE_PART & 1)  // timing-only build: the pairs are not stored
-                    if (skey[s] == 0x123456789abcdefull) a.out_a[bkt * a.stride_k + at] = skey[s] + sval[s];
-#else
-#if YH_GROUP_NT & 2  // (measured: the runs' stores no longer merge in the L2 -- 0.62 -> 1.08 GB written, +55 us)
-                    __builtin_nontemporal_store(skey[s], &a.out_a[bkt * a.stride_k + at]);
-                    __builtin_nontemporal_store(sval[s], &a.out_p[bkt * a.stride_v + at]);
-#else
+                    // (measured and dropped: non-temporal stores -- the runs' stores no longer merge in the L2: 0.62 -> 1.08 GB written, +55 us)
                     a.out_a[bkt * a.stride_k + at] = skey[s];
                     a.out_p[bkt * a.stride_v + at] = sval[s];
-#endif
-#endif
                 }
             }
         }
@@ -1346,7 +1250,7 @@ struct yh_psort {
 // Is this input one the distribution sort takes?  (A database of a few thousand hashes is one bucket; a key range narrower
 // than the number of fine slots cannot be spread: rocPRIM sorts those.)
 bool yh_psort_applicable(u64 H, u64 max_hash) {
-    static const bool off = [] { const char* e = yh_tune_env("YH_NO_PSORT"); return e && e[0] == '1'; }();
+    static const bool off = yh_tune_flag("YH_NO_PSORT");
     if (off || H == 0 || H > 0xfffffff0ull) return false;
     const u64 NB = (H + BKT_FILL - 1) / BKT_FILL;
     if (NB > (u64)PART_MAX_BINS * PART_MAX_BINS) return false;
@@ -1501,10 +1405,10 @@ static int second_level(yh_db* db, yh_psort* s) {
     return YH_OK;
 }
 static void say_verdict(const yh_psort* s, u32 flags, u64 total, bool took, const char* what) {
-    static const bool trace = [] { const char* e = yh_tune_env("YH_TRACE_BUILD"); return e && e[0] == '1'; }();
+    static const bool trace = yh_tune_flag("YH_TRACE_BUILD");
     if (trace || !took) {
         // (a refusal is worth a line even without the trace switch: the caller falls back to a sort three times as slow)
-        static const bool say = [] { const char* e = yh_tune_env("YH_TRACE_SORT"); return e && e[0] == '1'; }();
+        static const bool say = yh_tune_flag("YH_TRACE_SORT");
         if (trace || say)
             fprintf(stderr, "[yh sort] H %llu  P1 %u x P2 %u = %llu buckets  cap1 %llu  flags %u (1 region, 2 bucket, 4 slot)  %s %llu of %llu -> %s\n",
                     (u64)s->H, s->P1, s->P2, (u64)s->NB, (u64)s->cap1, flags, what, total, (u64)s->fed, took ? "taken" : "REFUSED");
@@ -1577,7 +1481,7 @@ int yh_psort_finish_emit(yh_db* db, yh_psort* s, u64* d_rec, u64 n_refs, u64 tot
     b.ref_tab = s->ref_tab;
     b.ref_off = s->ref_off;
     // (reference + 1 in 21 bits; YH_FZ_NO_INLINE=1 behind the tuning gate: every record in list form, as with >= 2^21 - 1 references)
-    static const bool no_inline = [] { const char* e = yh_tune_env("YH_FZ_NO_INLINE"); return e && e[0] == '1'; }();
+    static const bool no_inline = yh_tune_flag("YH_FZ_NO_INLINE");
     b.inline_ok = (n_refs < (1u << 21) - 1 && !no_inline) ? 1u : 0u;
     b.totals = s->totals;
     k_bucket_group<<<8u * b.per_xcd, BKT_THREADS, 0, db->stream>>>(b);
@@ -1633,7 +1537,7 @@ static unsigned bitlen64(u64 x) { unsigned b = 0; while (x) { ++b; x >>= 1; } re
 static bool pc_geometry(u64 H, u64 max_hash, u64 n_refs, yh_pieces* g) {
     if (!yh_psort_applicable(H, max_hash) || n_refs == 0 || max_hash == ~0ull) return false;
     static const double p2f = [] { const char* e = yh_tune_env("YH_PC_P2F"); return e ? atof(e) : 2.0; }();
-    static const u32 tile_elems = [] { const char* e = yh_tune_env("YH_PC_TILE_ELEMS"); return e ? (u32)atoi(e) : 3584u; }();
+    static const u32 tile_elems = (u32)yh_tune_int("YH_PC_TILE_ELEMS", 3584);
     const u64 nb = std::max<u64>((H + BKT_FILL - 1) / BKT_FILL, 1);
     u64 p2 = (u64)(p2f * std::sqrt((double)nb) + 0.5);
     p2 = std::min<u64>(std::max<u64>(p2, 1), PART_MAX_BINS);
@@ -1670,14 +1574,14 @@ static bool pc_geometry(u64 H, u64 max_hash, u64 n_refs, yh_pieces* g) {
     g->n_pad = (n_refs + 63) & ~(u64)63;
     const u64 tiles = 8ull * ((g->P1 + 7) / 8) * g->Gn;
     if (tiles >> 31) return false;
-    static const u32 pad = [] { const char* e = yh_tune_env("YH_PC_PAD"); return e ? (u32)atoi(e) : 0u; }();  // bytes (0, 128 ... 4 352 measured the same: profiles/r05/sweep_pad.txt)
+    static const u32 pad = (u32)yh_tune_int("YH_PC_PAD", 0);  // bytes (0, 128 ... 4 352 measured the same: profiles/r05/sweep_pad.txt)
     g->stride_k = BKT_CAP + pad / 8;
     g->stride_v = BKT_CAP + pad / 4;
     g->H = H; g->max_hash = max_hash; g->n_refs = n_refs;
     return true;
 }
 bool yh_pc_applicable(u64 H, u64 max_hash, u64 n_refs) {
-    static const bool off = [] { const char* e = yh_tune_env("YH_NO_PIECES"); return e && e[0] == '1'; }();
+    static const bool off = yh_tune_flag("YH_NO_PIECES");
     yh_pieces g;
     return !off && pc_geometry(H, max_hash, n_refs, &g);
 }
@@ -1699,7 +1603,7 @@ int yh_pc_begin(yh_db* db, u64 H, u64 max_hash, u64 n_refs, u64* d_rec, yh_piece
     if (e == hipSuccess) e = yh_tmalloc(db, (void**)&s->totals, TOT_LANES * 8 * sizeof(unsigned long long));
     // (the side list of overflowed buckets gets its room when a bucket HAS overflowed: a sixteenth of the pairs, at least a million --
     // more than that is not a database with a few hot k-mers but keys this distribution is not made for: refused)
-    static const bool no_spill = [] { const char* e_ = yh_tune_env("YH_NO_SPILL"); return e_ && e_[0] == '1'; }();
+    static const bool no_spill = yh_tune_flag("YH_NO_SPILL");
     s->spill_cap = no_spill ? 0 : std::max<u64>(H / 16, (u64)1 << 20);
     if (e == hipSuccess) e = hipMemsetAsync(s->cnt, 0, (s->NB + 4 + s->NB / 32 + 2) * sizeof(u32), db->stream);
     if (e == hipSuccess) e = hipMemsetAsync(s->totals, 0, TOT_LANES * 8 * sizeof(unsigned long long), db->stream);
@@ -1711,18 +1615,12 @@ int yh_pc_begin(yh_db* db, u64 H, u64 max_hash, u64 n_refs, u64* d_rec, yh_piece
     *out = s;
     return YH_OK;
 }
-// (the chained table of the two-level path, k_bucket_group, takes packed pairs too: YH_GROUP_CHAINS=1 behind the tuning gate; it
-// stores the records of shared hashes only, so with it the bounds pass clears them as it did until round 5)
-static bool pc_group_chains() {
-    static const bool chains = [] { const char* e = yh_tune_env("YH_GROUP_CHAINS"); return e && e[0] == '1'; }();
-    return chains;
-}
+// (the pairwise records are not cleared anywhere on this path: k_bucket_group5 and k_spill_group write every position's record)
 static PieceArgs pc_args(const yh_pieces* s, const u64* d_values, const u64* d_offsets) {
     PieceArgs a{};
     a.values = d_values; a.off = d_offsets; a.n_refs = s->n_refs; a.bnd = s->bnd; a.n_pad = s->n_pad;
     a.P1 = s->P1; a.P2 = s->P2; a.S = s->S; a.Gn = s->Gn; a.SK = s->SK;
     a.mul = s->mul_fine; a.lsh = s->lsh; a.rem_bits = s->rem_bits; a.inv_p2 = s->inv_p2;
-    a.rec_clear = pc_group_chains() ? s->rec : nullptr;  // (k_bucket_group5 writes every position's record itself)
     a.out_a = s->a2; a.out_p = s->p2; a.out_cnt = s->cnt; a.flags = s->cnt + s->NB;
     a.stride_k = s->stride_k; a.stride_v = s->stride_v;
     a.spill_a = s->spill_a; a.spill_p = s->spill_p; a.spill_b = s->spill_b; a.spill_cap = s->spill_cap;
@@ -1761,7 +1659,7 @@ static int pc_collect_spill(yh_db* db, yh_pieces* s, const u64* d_values, const 
     return YH_OK;
 }
 
-// distribution + the fused last pass (k_bucket_group on packed pairs): as yh_psort_finish_emit
+// distribution + the fused last pass (k_bucket_group5): as yh_psort_finish_emit
 int yh_pc_finish_emit(yh_db* db, yh_pieces* s, const u64* d_values, const u64* d_offsets, u64 totals[3], u32** d_list_out, bool* took_it,
                       bool* unsorted, yh_pc_spill* spill) {
     *took_it = false;
@@ -1787,13 +1685,10 @@ int yh_pc_finish_emit(yh_db* db, yh_pieces* s, const u64* d_values, const u64* d
     b.list = s->p2;
     b.rem_bits = s->rem_bits;
     b.over_bits = s->spill_cap ? s->cnt + s->NB + 4 : nullptr;
-    static const bool no_inline = [] { const char* e = yh_tune_env("YH_FZ_NO_INLINE"); return e && e[0] == '1'; }();
+    static const bool no_inline = yh_tune_flag("YH_FZ_NO_INLINE");
     b.inline_ok = (s->n_refs < (1u << 21) - 1 && !no_inline) ? 1u : 0u;
     b.totals = s->totals;
-    const bool chains = pc_group_chains();
-    b.write_all = chains ? 0u : 1u;
-    if (!chains) k_bucket_group5<<<8u * b.per_xcd, BKT_THREADS, 0, db->stream>>>(b);
-    else k_bucket_group<<<8u * b.per_xcd, BKT_THREADS, 0, db->stream>>>(b);
+    k_bucket_group5<<<8u * b.per_xcd, BKT_THREADS, 0, db->stream>>>(b);
     YH_HIP(hipGetLastError());
     unsigned long long ht[4] = {0, 0, 0, 0};
     static thread_local unsigned long long hrows_pageable[TOT_LANES * 8 + 2];
@@ -1849,7 +1744,7 @@ int yh_pc_finish_emit(yh_db* db, yh_pieces* s, const u64* d_values, const u64* d
     }
     *took_it = spill_ok && (hflags[0] & 7u) == 0 && ht[3] == s->H && s->scanned == s->H && !(hflags[0] & 8u);
     if (unsorted) *unsorted = (hflags[0] & 8u) != 0;
-    static const bool trace = [] { const char* e = yh_tune_env("YH_TRACE_BUILD"); const char* f = yh_tune_env("YH_TRACE_SORT"); return (e && e[0] == '1') || (f && f[0] == '1'); }();
+    static const bool trace = yh_tune_flag("YH_TRACE_BUILD") || yh_tune_flag("YH_TRACE_SORT");
     if (trace)
         fprintf(stderr, "[yh pieces] H %llu  P1 %u x P2 %u = %llu buckets  S %u x Gn %u  SK %u  rem_bits %u  flags %u  records of %llu of %llu -> %s\n",
                 (u64)s->H, s->P1, s->P2, (u64)s->NB, s->S, s->Gn, s->SK, s->rem_bits, hflags[0], (u64)ht[3], (u64)s->H, *took_it ? "taken" : "REFUSED");
@@ -1896,7 +1791,6 @@ int yh_pc_sort(yh_db* db, const u64* d_values, const u64* d_offsets, u64 n_refs,
     if (rc != YH_OK) return fail(rc);
     PieceArgs a = pc_args(s, d_values, d_offsets);
     a.emit_ref = 1u;
-    a.rec_clear = nullptr;
     k_piece_part<true><<<8u * ((s->P1 + 7) / 8) * s->Gn, PART_THREADS, 0, db->stream>>>(a);
     u32* flags = s->cnt + s->NB;
     k_bucket_offsets<<<1, 1024, 0, db->stream>>>(s->cnt, s->NB, s->spill_cap ? 0u : BKT_CAP, off, flags);
@@ -1954,7 +1848,7 @@ int yh_pc_sort(yh_db* db, const u64* d_values, const u64* d_offsets, u64 n_refs,
         }
     }
     if (unsorted) *unsorted = (hflags[0] & 8u) != 0;
-    static const bool trace = [] { const char* e_ = yh_tune_env("YH_TRACE_BUILD"); const char* f = yh_tune_env("YH_TRACE_SORT"); return (e_ && e_[0] == '1') || (f && f[0] == '1'); }();
+    static const bool trace = yh_tune_flag("YH_TRACE_BUILD") || yh_tune_flag("YH_TRACE_SORT");
     if (trace)
         fprintf(stderr, "[yh pieces] H %llu  P1 %u x P2 %u = %llu buckets  S %u x Gn %u  flags %u  sorted %llu of %llu  side list %llu pairs of %u buckets -> %s\n",
                 (u64)H, s->P1, s->P2, (u64)s->NB, s->S, s->Gn, hflags[0], (u64)total, (u64)H, (u64)n_spill, hflags[2], ok ? "taken" : "REFUSED");
