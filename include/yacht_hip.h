@@ -295,6 +295,7 @@ int yh_run_device_join(yh_db* db);
  *     yh_db_synchronize, yh_db_get_timing, yh_db_get_info    |   pipelined stages)                    |
  *   yh_pairwise, yh_index_stats, yh_db_nshared_device        | yes                                   | yes
  *   yh_abund / yh_abund_device                               | yes (no step state is read or written) | yes
+ *   yh_abund_batch / yh_abund_batch_device                   | yes (no step state is read or written) | yes
  *   yh_explain / yh_explain_device                           | yes (no step state is read or written) | yes
  *   yh_explain_batch / yh_explain_batch_device,              | yes (no step state is read or written) | yes
  *     yh_explain_members_rows_device                         |                                       |
@@ -431,6 +432,37 @@ int yh_abund_device(yh_db* db, const uint64_t* d_sample, const uint32_t* d_abund
                     uint64_t* d_w_overlap, uint64_t* d_w_match, double* d_med_match);   /* [N] each */
 int yh_abund(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_t n_sample,
              uint64_t* w_overlap, uint64_t* w_match, double* med_match);
+
+/* ---- the same for a BLOCK of samples (additive in ABI 8) ------------------------------------------------------------------------
+ * yh_abund_batch_device answers 1..YH_BATCH_MAX_SAMPLES samples in a number of launches that does not depend on n_samples: one
+ * clear of the three outputs, ONE lookup launch, and for the medians one segmented sort of the single-holder hits inside each
+ * sample's own segment of a key buffer and one kernel that stores the median of every (sample, reference) run that exists.
+ * The samples are laid out as for yh_run_batch_device: d_samples holds them back to back (each strictly ascending),
+ * d_sample_offsets[n_samples + 1] delimits them, d_abund runs in parallel to d_samples.  total_hashes is the CALLER's copy of
+ * d_sample_offsets[n_samples] (the offsets are never read on the host), as for yh_explain_batch_device: it sizes the launch and
+ * the key buffer and decides the "no hashes" case; the kernels walk the samples by the device offsets alone.  A larger
+ * total_hashes costs idle workgroups and memory; a smaller one costs time -- the medians of a sample that ends behind
+ * total_hashes are found by counting ranks, without a key buffer, quadratic in its length -- and never a wrong cell.
+ * total_hashes == 0 looks nothing up and gives zeroed rows, whatever the device offsets hold.  The offsets must ascend and stay
+ * inside d_samples and d_abund: they are not checked.  With medians total_hashes must stay below 2^32 (YH_ERR_INVALID_ARG).
+ * Contract: for every sample s, row s of each output (leading dimension N) is bit-identical to what yh_abund_device returns
+ * for that sample alone: integer sums, and medians that are x.0 or x.5, 0.0 for an empty set.  Every cell of the first
+ * n_samples rows is written by every call (nothing of an earlier, larger block survives; an empty database or total_hashes
+ * == 0 gives zeroed rows), and nothing outside those rows.  d_med_match / med_match may be NULL: the sums only, with no key
+ * buffer and no sort.  A workgroup looks up a tile of YH_ABUND_BATCH_TILE consecutive hashes of one sample.  Like
+ * yh_abund_device the pass reads no step context, batch slot or work list (interleaving table above: yes / yes), completes
+ * pending pipelined stages first, is enqueued on the handle's stream and does not sync the host.  n_samples == 0 or >
+ * YH_BATCH_MAX_SAMPLES: YH_ERR_INVALID_ARG.  YH_ERR_UNSUPPORTED as for yh_abund_device.
+ * yh_abund_batch is the synchronous host form: it checks every sample's ordering (YH_ERR_UNSORTED), then uploads, runs and
+ * downloads; the three outputs are [n_samples][N].  Nothing is built for shards, and there is no rows form.                   */
+#ifndef YH_ABUND_BATCH_TILE
+#define YH_ABUND_BATCH_TILE 1024
+#endif
+int yh_abund_batch_device(yh_db* db, const uint64_t* d_samples, const uint64_t* d_sample_offsets /* [n_samples + 1] */,
+                          const uint32_t* d_abund /* [total_hashes] */, uint32_t n_samples, uint64_t total_hashes,
+                          uint64_t* d_w_overlap, uint64_t* d_w_match, double* d_med_match /* or NULL */);   /* [n_samples][N] each */
+int yh_abund_batch(yh_db* db, const uint64_t* samples, const uint64_t* sample_offsets, const uint32_t* abund,
+                   uint32_t n_samples, uint64_t* w_overlap, uint64_t* w_match, double* med_match /* or NULL */);
 
 /* ---- what of a sample a set of references EXPLAINS, per sample hash (additive in ABI 8) --------------------------------------
  * Every query above reduces over the sample and answers per reference; this one answers per SAMPLE HASH.  Inputs: the sample S

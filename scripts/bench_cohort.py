@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """`yacht run` over a cohort (yacht_amd/cohort.py) end to end, on a synthetic database with real-shape samples.
 
-    python scripts/bench_cohort.py [--n-refs 85205] [--samples 1024] [--single 32] [--residual] [--commit ID] [--out FILE]
+    python scripts/bench_cohort.py [--n-refs 85205] [--samples 1024] [--single 32] [--residual] [--abundance] [--commit ID] [--out FILE]
 
 Prints one JSON line: samples/s of the cohort command with its phase split (yacht_amd/cohort.py main: check, db, table,
 device_setup, parse_wait, device_wait, the device time of uploads / batch counts + compact rows / presence kernel, d2h,
 assemble, writes), the presence kernel alone against yh_hyp_test (host) over the same rows, and `--single` of the samples
 through the single-sample command in the same process (warm) for comparison.  --residual runs the cohort (and the single
-commands) with `yacht run --residual`: gpu_explain is then the phase of the residual's device work.  --commit is recorded."""
+commands) with `yacht run --residual`: gpu_explain is then the phase of the residual's device work.  --abundance runs them with `yacht run --abundance`: gpu_abund is
+the device time of the blocks' depth passes (YACHT_COHORT_ABUND=loop in the environment: the per-sample loop).  --commit is
+recorded."""
 from __future__ import annotations
 
 import argparse
@@ -128,6 +130,7 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--seed", type=int, default=1002)
     ap.add_argument("--residual", action="store_true")
+    ap.add_argument("--abundance", action="store_true")
     ap.add_argument("--commit", default="")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -141,7 +144,8 @@ def main():
     out = os.path.join(tmp, "cohort_out")
     os.makedirs(out)
     args = SimpleNamespace(json=cfg, sample_file=paths, significance=0.99, num_threads=a.threads, keep_raw=False, show_all=False,
-                           min_coverage_list=COVS, outdir=out, residual=a.residual, residual_coverage=None)
+                           min_coverage_list=COVS, outdir=out, residual=a.residual, residual_coverage=None,
+                           abundance=a.abundance)
     t0 = time.perf_counter()
     phases = cohort.main(args, paths)
     wall = time.perf_counter() - t0
@@ -164,6 +168,8 @@ def main():
                     f"~{a.sample_hashes} hashes as .sig.zip, coverages {COVS}",
         "commit": a.commit,
         "residual": bool(a.residual),
+        "abundance": bool(a.abundance),
+        "cohort_abund": os.environ.get("YACHT_COHORT_ABUND", ""),
         "setup_s": round(setup_s, 1),
         "bottleneck": None,
         "cohort": {"samples": a.samples, "wall_s": round(wall, 2), "samples_per_s": round(a.samples / wall, 2),

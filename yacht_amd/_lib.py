@@ -31,6 +31,7 @@ YH_BATCH_SLOTS = 3
 YH_BATCH_MAX_SAMPLES = 256
 YH_PRESENCE_MAX_COVS = 16
 YH_EXPLAIN_BATCH_TILE = 2048
+YH_ABUND_BATCH_TILE = 1024
 YH_LOOKUP_AUTO, YH_LOOKUP_STREAM, YH_LOOKUP_INDEXED = 0, 1, 2
 
 _ERR_NAMES = {
@@ -151,6 +152,8 @@ SIGNATURES = {
     "yh_run_rows_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
     "yh_abund": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "yh_abund_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "yh_abund_batch_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp]),
+    "yh_abund_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
     "yh_explain": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "yh_explain_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "yh_explain_members_rows_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_uint32, _vp]),

@@ -169,7 +169,9 @@ class _Device:
         self._alloc(int(cap) if cap > 0 else min(BLOCK * max(N, 1), 1 << 20))
         self.ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
         self.abund = None
-        if abund_samples > 0:  # [samples][N] sums and medians of a block (yh_abund_device, one call per sample)
+        if abund_samples > 0:  # [samples][N] sums and medians of a block (yh_abund_batch_device, one call per block)
+            # YACHT_COHORT_ABUND=loop: yh_abund_device once per sample, as before the batched pass (an A/B switch: same files)
+            self.abund_loop = os.environ.get("YACHT_COHORT_ABUND") == "loop"
             shape = (int(abund_samples), max(N, 1))
             self.abund = (torch.zeros(shape, dtype=torch.int64, device=self.dev), torch.zeros(shape, dtype=torch.int64, device=self.dev),
                           torch.zeros(shape, dtype=torch.float64, device=self.dev))
@@ -213,12 +215,17 @@ class _Device:
                                                    C.c_void_p(out[2][c0].data_ptr())))
 
     def abundance_pass(self, offs: np.ndarray, b: int) -> None:
-        """The block's abundance pass: yh_abund_device once per sample on its slice of the uploaded block, then the three
-        values of every compact row (sample, reference) gathered on the device."""
+        """The block's abundance pass: one yh_abund_batch_device over the uploaded block (YACHT_COHORT_ABUND=loop:
+        yh_abund_device once per sample on its slice, as before the batched pass; the same values), then the three values
+        of every compact row (sample, reference) gathered on the device."""
         w_ov, w_m, med = self.abund
-        for s in range(b):
-            self.db.abundance_device(self.d_samples.data_ptr() + 8 * int(offs[s]), self.d_abund.data_ptr() + 4 * int(offs[s]),
-                                     int(offs[s + 1] - offs[s]), w_ov[s].data_ptr(), w_m[s].data_ptr(), med[s].data_ptr())
+        if self.abund_loop:
+            for s in range(b):
+                self.db.abundance_device(self.d_samples.data_ptr() + 8 * int(offs[s]), self.d_abund.data_ptr() + 4 * int(offs[s]),
+                                         int(offs[s + 1] - offs[s]), w_ov[s].data_ptr(), w_m[s].data_ptr(), med[s].data_ptr())
+        else:
+            self.db.abundance_batch_device(self.d_samples.data_ptr(), self.d_offs.data_ptr(), self.d_abund.data_ptr(), b,
+                                           int(offs[b]), w_ov.data_ptr(), w_m.data_ptr(), med.data_ptr())
         self.abund_rows = self.gather_abundance(self.rows, b)
 
     def gather_abundance(self, rows, b: int):
@@ -351,8 +358,8 @@ def main(args, files: List[str]) -> dict:
     check (every input, samples parsed once), db (database build), table (the per-n threshold table), device_setup (torch
     and the device buffers), parse_wait (the loop waiting for a block's sketches), device_wait (the loop waiting for a
     block's device work), gpu_h2d / gpu_counts / gpu_presence (device time of the uploads, the batch counts + compact rows,
-    the presence kernel), gpu_abund (with --abundance: the block's yh_abund_device calls and the gather of their values at the
-    compact rows), gpu_explain (with --residual: device time of the block's member-row and batched explain passes, plus
+    the presence kernel), gpu_abund (with --abundance: the block's yh_abund_batch_device call -- its yh_abund_device calls under
+    YACHT_COHORT_ABUND=loop -- and the gather of their values at the compact rows), gpu_explain (with --residual: device time of the block's member-row and batched explain passes, plus
     the wall time of the host-form yh_explain calls of samples whose tables the host recomputed, or of every sample under
     YACHT_COHORT_EXPLAIN=host), d2h, assemble, writes (what the write pool had left after the last block), cohort_files (the two
     cohort tables), total."""

@@ -1186,6 +1186,78 @@ int yh_abund(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_t 
     return rc;
 }
 
+// ---- the same for a block of samples ----
+static bool abund_batch_samples_ok(uint32_t n_samples) {
+    if (n_samples >= 1 && n_samples <= YH_BATCH_MAX_SAMPLES) return true;
+    yh_set_error("1..%d samples per batch", YH_BATCH_MAX_SAMPLES);
+    return false;
+}
+
+int yh_abund_batch_device(yh_db* db, const uint64_t* d_samples, const uint64_t* d_sample_offsets, const uint32_t* d_abund,
+                          uint32_t n_samples, uint64_t total_hashes, uint64_t* d_w_overlap, uint64_t* d_w_match, double* d_med_match) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (!abund_batch_samples_ok(n_samples)) return YH_ERR_INVALID_ARG;
+    if (!d_w_overlap || !d_w_match || !d_sample_offsets || (total_hashes && (!d_samples || !d_abund))) {
+        yh_set_error("null device pointer");
+        return YH_ERR_INVALID_ARG;
+    }
+    YH_TRY(abund_supported(db));
+    YH_TRY(db_select(db));
+    YH_TRY(pipe_join(db));  // (no step context, batch slot or work list is read or written: nothing else to note)
+    return yh_q_abund_batch(db, (const u64*)d_samples, (const u64*)d_sample_offsets, d_abund, n_samples, total_hashes,
+                            (u64*)d_w_overlap, (u64*)d_w_match, d_med_match);
+}
+
+int yh_abund_batch(yh_db* db, const uint64_t* samples, const uint64_t* sample_offsets, const uint32_t* abund, uint32_t n_samples,
+                   uint64_t* w_overlap, uint64_t* w_match, double* med_match) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (!abund_batch_samples_ok(n_samples)) return YH_ERR_INVALID_ARG;
+    if (!sample_offsets) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+    const u64 total = sample_offsets[n_samples];
+    const u64 N = db->n_refs;
+    const u64 BN = (u64)n_samples * N;
+    if (sample_offsets[0] != 0 || (total && (!samples || !abund)) || (N && (!w_overlap || !w_match))) {
+        yh_set_error("bad sample arrays or null output");
+        return YH_ERR_INVALID_ARG;
+    }
+    for (uint32_t s = 0; s < n_samples; ++s) {
+        if (sample_offsets[s + 1] < sample_offsets[s] ||
+            yh_q_check_sorted_host((const u64*)samples + sample_offsets[s], sample_offsets[s + 1] - sample_offsets[s]) != YH_OK) {
+            yh_set_error("sample %u is not strictly ascending", s);
+            return YH_ERR_UNSORTED;
+        }
+    }
+    YH_TRY(abund_supported(db));
+    YH_TRY(db_select(db));
+    if (N == 0) return YH_OK;
+    u64 *d_s = nullptr, *d_o = nullptr, *d_out = nullptr;
+    u32* d_a = nullptr;
+    int rc = YH_OK;
+    do {
+        if (yh_tmalloc(db, (void**)&d_s, std::max<u64>(total, 2) * sizeof(u64)) != hipSuccess ||
+            yh_tmalloc(db, (void**)&d_o, (u64)(n_samples + 1) * sizeof(u64)) != hipSuccess ||
+            yh_tmalloc(db, (void**)&d_a, std::max<u64>(total, 4) * sizeof(u32)) != hipSuccess ||
+            yh_tmalloc(db, (void**)&d_out, 3 * BN * sizeof(u64)) != hipSuccess) { yh_set_error("device allocation failed"); rc = YH_ERR_OOM; break; }
+        if ((total && hipMemcpyAsync(d_s, samples, total * sizeof(u64), hipMemcpyHostToDevice, db->stream) != hipSuccess) ||
+            hipMemcpyAsync(d_o, sample_offsets, (u64)(n_samples + 1) * sizeof(u64), hipMemcpyHostToDevice, db->stream) != hipSuccess ||
+            (total && hipMemcpyAsync(d_a, abund, total * sizeof(u32), hipMemcpyHostToDevice, db->stream) != hipSuccess)) {
+            yh_set_error("abundance upload failed"); rc = YH_ERR_HIP; break;
+        }
+        double* const d_med = med_match ? (double*)(d_out + 2 * BN) : nullptr;
+        if ((rc = yh_abund_batch_device(db, (const uint64_t*)d_s, (const uint64_t*)d_o, d_a, n_samples, total, (uint64_t*)d_out,
+                                        (uint64_t*)(d_out + BN), d_med)) != YH_OK) break;
+        const bool down_ok = hipMemcpyAsync(w_overlap, d_out, BN * sizeof(u64), hipMemcpyDeviceToHost, db->stream) == hipSuccess &&
+                             hipMemcpyAsync(w_match, d_out + BN, BN * sizeof(u64), hipMemcpyDeviceToHost, db->stream) == hipSuccess &&
+                             (!med_match || hipMemcpyAsync(med_match, d_med, BN * sizeof(double), hipMemcpyDeviceToHost, db->stream) == hipSuccess);
+        if (!down_ok || hipStreamSynchronize(db->stream) != hipSuccess) {
+            yh_set_error("abundance download failed: %s", hipGetErrorString(hipGetLastError()));
+            rc = YH_ERR_HIP;
+        }
+    } while (0);
+    yh_tfree(db, d_s); yh_tfree(db, d_o); yh_tfree(db, d_a); yh_tfree(db, d_out);
+    return rc;
+}
+
 // ---- what of a sample the members of up to seven call sets explain, per sample hash (yh_explain.hip) -----------
 static int explain_supported(yh_db* db) {
     if (!db->has_dir || !db->has_index || (db->n_shared && (!db->d_po || !db->d_pr))) {

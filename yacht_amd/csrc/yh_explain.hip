@@ -149,11 +149,6 @@ struct ExplainBatch {
     u64* totals;  // [n_samples][8][2], cleared in front of this launch
 };
 
-// a workgroup-uniform value read from LDS, back in scalar registers (the loop state of a tile then costs no vector registers)
-__device__ __forceinline__ u64 uniform64(u64 v) {
-    return ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(v >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)v);
-}
-
 __global__ void __launch_bounds__(XB_THREADS) k_explain_batch_lookup(const ExplainBatch q) {
     __shared__ u64 off[XB_MAX + 1];
     __shared__ u64 s_max_nt;

@@ -1,6 +1,6 @@
 // yh_lookup.h — the ONE place the distinct-hash directory (YhDirView, yh_common.h) is probed from by the tile kernels:
-// k_index_lookup_tile / k_step_fused (yh_query.hip: lookup_tile_body), k_abund_lookup (yh_abund.hip), k_explain_lookup
-// (yh_explain.hip) and k_batch_lookup (yh_batch.hip).  Device code, plus the host-side table of the tile shapes.
+// k_index_lookup_tile / k_step_fused (yh_query.hip: lookup_tile_body), k_abund_lookup / k_abund_batch_lookup (yh_abund.hip),
+// k_explain_lookup (yh_explain.hip) and k_batch_lookup (yh_batch.hip).  Device code, plus the host-side table of the tile shapes.
 //
 // A lane holds U sample hashes h[u] with ok[u] = "still worth looking up".  A hash that is not (past the sample's end, or
 // above the database's largest hash) is set to 0 by the kernel: 0 is still a valid filter word and bucket to read, so
@@ -83,6 +83,11 @@ template <int U>
 __device__ __forceinline__ u32 yh_probe_resolve(const YhDirView& dv, const u64 (&h)[U], const bool (&ok)[U], const YhProbe<U>& p, int u) {
     if (!ok[u]) return YH_DIR_NONE;
     return dv.cbkt ? dv.cbkt_resolve(h[u], p.a[u], p.b[u], p.c[u], p.d[u]) : dv.find(h[u]);
+}
+
+// a workgroup-uniform value read from LDS, back in scalar registers (the loop state of a tile then costs no vector registers)
+__device__ __forceinline__ u64 uniform64(u64 v) {
+    return ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(v >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)v);
 }
 
 // The slot of reference `ref` in a workgroup's LDS hit table of 2^TBITS keys (tkey: reference + 1, 0 = empty), claimed

@@ -284,6 +284,33 @@ class RefDB:
         _lib.check(self._lib.yh_abund_device(self._h, C.c_void_p(d_sample), C.c_void_p(d_abund), n_sample, C.c_void_p(d_w_overlap),
                                              C.c_void_p(d_w_match), C.c_void_p(d_med)))
 
+    def abundance_batch(self, samples: Sequence[np.ndarray], abunds, want_median: bool = True):
+        """abundance for a block of 1..256 samples in a fixed number of launches (yh_abund_batch).  abunds: one array per
+        sample, one abundance per hash.  Returns (w_overlap, w_match, med_match): uint64 [len(samples), n_refs] twice and
+        float64 [len(samples), n_refs] (None with want_median=False: the sums only, without the sort); row s equals
+        abundance's for sample s alone."""
+        b = len(samples)
+        if not 1 <= b <= _lib.YH_BATCH_MAX_SAMPLES:
+            raise ValueError(f"a block holds 1..{_lib.YH_BATCH_MAX_SAMPLES} samples, not {b}")
+        if len(abunds) != b:
+            raise ValueError(f"{len(abunds)} abundance arrays for {b} samples")
+        pairs = [check_abundances(s, a) for s, a in zip(samples, abunds)]
+        values, offsets = pack_csr([p[0] for p in pairs])
+        cat_ab = np.ascontiguousarray(np.concatenate([p[1] for p in pairs]), dtype=np.uint32)
+        w_ov = np.zeros((b, self.n_refs), dtype=np.uint64)
+        w_m = np.zeros((b, self.n_refs), dtype=np.uint64)
+        med = np.zeros((b, self.n_refs), dtype=np.float64) if want_median else None
+        _lib.check(self._lib.yh_abund_batch(self._h, _ptr(values), _ptr(offsets), _ptr(cat_ab), b, _ptr(w_ov), _ptr(w_m), _ptr(med)))
+        return w_ov, w_m, med
+
+    def abundance_batch_device(self, d_samples: int, d_offsets: int, d_abund: int, n_samples: int, total_hashes: int,
+                               d_w_overlap: int, d_w_match: int, d_med: int = 0) -> None:
+        """yh_abund_batch_device: the block as for run_batch_device and uint32 abundances beside the hashes in, uint64
+        [n_samples][N] sums and (d_med != 0) float64 [n_samples][N] medians out."""
+        _lib.check(self._lib.yh_abund_batch_device(self._h, C.c_void_p(d_samples), C.c_void_p(d_offsets), C.c_void_p(d_abund),
+                                                   n_samples, total_hashes, C.c_void_p(d_w_overlap), C.c_void_p(d_w_match),
+                                                   C.c_void_p(d_med)))
+
     def explain(self, sample, member, abund=None, want_flags: bool = True) -> Tuple[Optional[np.ndarray], np.ndarray]:
         """What the call sets of `member` explain of the sample (yh_explain).  member: uint8 [n_refs], bit k (0..6) = the
         reference belongs to call set k.  abund: one abundance per sample hash, or None (all 1).  Returns (flags, totals):
