@@ -377,8 +377,8 @@ struct WaveQ {
     u64x2* q;      // LDS: this wave's STREAM_WQ entries (x = stream position, y = sample index)
     u32 wg;
     u32* tkey;     // LDS: the workgroup's per-reference hit sums, STREAM_TSLOTS slots (reference + 1, 0 = empty)
-    u32* tcnt;     // hits: low 16 bits of the slot's increments count all hits ...
-    u32* tcnt2;    // ... and this one the hits on shared hashes
+    u32* tcnt;     // LDS: per slot, a 32-bit count of all hits ...
+    u32* tcnt2;    // ... and of the hits on shared hashes
 };
 // Confirmed hits are summed per reference in an LDS table of the workgroup and leave as ONE global
 // atomic per (workgroup, reference) when the workgroup ends: in hash order a reference's hits are
@@ -466,12 +466,16 @@ __device__ __forceinline__ void wave_flush(const StreamHit& hit, const WaveQ& c,
     __builtin_amdgcn_wave_barrier();
 }
 
-// wg_key[w] = t of the first element of workgroup w's block range (~0 past the end): sample-independent
-__global__ void k_wg_key(const u64* __restrict__ hdr, u64 nblk, u32 wgs, u64* __restrict__ wg_key) {
+// wg_key[w] = t of the first element of workgroup w's block range, sample-independent.  Past the end: last_key, the
+// stream's largest key (max_hash >> sshift) -- no element lies above it and the upper bound of a range is inclusive, so
+// the last range ends there and sample hashes above the database's largest are staged by nobody.  (With all ones
+// there, such hashes more than 2^32 keys apart made one tile each: DESIGN.md 3.)
+__global__ void k_wg_key(const u64* __restrict__ hdr, u64 nblk, u32 wgs, u64 last_key, u64* __restrict__ wg_key) {
     const u32 w = blockIdx.x * blockDim.x + threadIdx.x;
     if (w > wgs) return;
     const u64 per = (nblk + wgs - 1) / wgs;
-    wg_key[w] = hdr[min((u64)w * per, nblk)];
+    const u64 b = (u64)w * per;
+    wg_key[w] = b < nblk ? hdr[b] : last_key;
 }
 
 // A workgroup's sample range [lo, hi) = the sample hashes with wg_key[w] <= t <= wg_key[w + 1]
@@ -1236,7 +1240,7 @@ static int yh_q_overlap_stream(yh_db* db, const u64* d_sample, u64 n_sample, u32
         YH_HIP(hipStreamSynchronize(st));
         if (db->d_wg_key) { yh_dfree(db, db->d_wg_key); db->d_wg_key = nullptr; }
         YH_HIP(hipMalloc((void**)&db->d_wg_key, ((u64)wgs + 2) * sizeof(u64)));
-        k_wg_key<<<(wgs + 256) / 256, 256, 0, st>>>(db->d_shdr, nblk, wgs, db->d_wg_key);
+        k_wg_key<<<(wgs + 256) / 256, 256, 0, st>>>(db->d_shdr, nblk, wgs, db->max_hash >> db->sshift, db->d_wg_key);
         db->wg_key_n = wgs;
     }
     u32 R;
