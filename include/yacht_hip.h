@@ -299,6 +299,7 @@ int yh_run_device_join(yh_db* db);
  *   yh_explain / yh_explain_device                           | yes (no step state is read or written) | yes
  *   yh_explain_batch / yh_explain_batch_device,              | yes (no step state is read or written) | yes
  *     yh_explain_members_rows_device                         |                                       |
+ *   yh_gather / yh_gather_device                             | yes (no step state is read or written) | yes
  *   yh_db_set_stream                                         | yes (drains the old stream first)      | yes
  *   (*) the CURRENT context = the one named by the last yh_run_local*_device / yh_run_finish*_device call (0 at start).
  * Every query entry point first completes the pending stages of pipelined steps (yh_run_device_join) by itself.          */
@@ -534,6 +535,52 @@ int yh_explain_batch_device(yh_db* db, const uint64_t* d_samples, const uint64_t
                             uint64_t* d_totals /* [n_samples][8][2] */);
 int yh_explain_batch(yh_db* db, const uint64_t* samples, const uint64_t* sample_offsets, const uint32_t* abund, uint32_t n_samples,
                      const uint8_t* members, uint8_t* flags, uint64_t* totals);
+
+/* ---- the candidate references RANKED by the sample hashes each adds: a minimum set cover (additive in ABI 8) ------------------
+ * yh_run judges every reference on its own and yh_explain answers for a call set as a whole; this divides the explained part
+ * of the sample among the candidates, greedily, like `sourmash gather`.  Inputs: the sample S (strictly ascending, n_sample <
+ * 2^32), optional abundances abund(h) (NULL: every abund(h) = 1), a candidate table cand[N] of one byte per reference (non-zero
+ * = candidate), min_hits >= 1 and a row capacity cap_rows.  State: a sample hash is LIVE while nobody owns it, and for every
+ * candidate j, c[j] = the number of live sample hashes j holds.  Holders that are not candidates never count, never win and
+ * never block: a hash held by one candidate and five others is that candidate's.  Round k = 0, 1, ...:
+ *   j* = the candidate with the largest c[j], ties to the smallest reference index; stop when there is none or c[j*] < min_hits;
+ *   otherwise row k = { ref = j*, n_overlap = c[j*] as it was before round 0 (|S ∩ R_j*|), n_unique = c[j*],
+ *                       w_unique = sum of abund(h) over the live hashes j* holds };
+ *   every such hash gets owner j*, and every candidate holder of every such hash loses one from its count.
+ * The run also stops when k == cap_rows; *more = 1 exactly when it stopped there while a candidate with c >= min_hits remained,
+ * otherwise 0 (so cap_rows == 0 with an eligible candidate gives no row and *more = 1).  Outputs: *n_rows, the rows, *more and,
+ * when owner / d_owner is not NULL, owner[n_sample]: the reference that took the hash, 0xFFFFFFFF = nobody.  Rows behind
+ * *n_rows are not written.  All integers; nothing depends on arrival order.  Consequences: n_unique never increases from row
+ * to row; with min_hits = 1 and cap_rows >= N the n_unique add up to yh_explain's totals[b][0] for the member table
+ * (cand != 0) << b and the w_unique to totals[b][1]; row 0's n_unique is the largest yh_run overlap among the candidates;
+ * owner[i] != nobody exactly where yh_explain's flag has bit b.
+ * n_sample == 0, an empty database, no candidate or cap_rows == 0: zero rows, *more = 0 (but see cap_rows == 0 above), owner
+ * all "nobody".  min_hits == 0: YH_ERR_INVALID_ARG.
+ * How it runs: one directory lookup of the sample (single-holder hits are summed per candidate and never looked at again; the
+ * shared hits with a candidate holder go on a live list), then two small launches per round -- pick the winner, claim its
+ * live shared hits -- with the kernel boundary as the only ordering between workgroups.  The rounds are enqueued
+ * YH_GATHER_ROUNDS_PER_SYNC at a time; rounds behind the end do nothing.  n_rows and more are HOST pointers: the device form
+ * DOES synchronize the host with the handle's stream once per chunk -- the first query entry whose device form does -- and
+ * returns with rows complete and the owner fix-up enqueued.  It reads no step context, batch slot or work list
+ * (interleaving table above: yes / yes), completes pending pipelined stages first like every query entry, and waits for a
+ * finish stream's second half like the other entries that follow one.  The host form is synchronous, validates the sample's
+ * ordering (YH_ERR_UNSORTED), uploads, runs and downloads.
+ * YH_ERR_UNSUPPORTED exactly where yh_explain returns it: a handle without the directory or the index (YH_DB_NO_DIRECTORY,
+ * YH_DB_NO_INDEX, YH_DB_PAIRWISE_ONLY), or with ghosts registered (yh_db_set_ghosts).
+ * Nothing is built for shards or for blocks of samples.
+ * (No reference counterpart: its use-case scripts subtract sketches with Python sets.)                                        */
+typedef struct yh_gather_row {
+    uint32_t ref, n_overlap, n_unique, reserved_;
+    uint64_t w_unique;
+} yh_gather_row;
+#ifndef YH_GATHER_ROUNDS_PER_SYNC
+#define YH_GATHER_ROUNDS_PER_SYNC 32
+#endif
+int yh_gather_device(yh_db* db, const uint64_t* d_sample, const uint32_t* d_abund /* NULL: all 1 */, uint64_t n_sample,
+                     const uint8_t* d_cand /* [N] */, uint32_t min_hits, yh_gather_row* d_rows /* [cap_rows] */, uint64_t cap_rows,
+                     uint32_t* d_owner /* [n_sample] or NULL */, uint64_t* n_rows /* HOST */, int* more /* HOST */);
+int yh_gather(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_t n_sample, const uint8_t* cand,
+              uint32_t min_hits, yh_gather_row* rows, uint64_t cap_rows, uint32_t* owner, uint64_t* n_rows, int* more);
 
 /* ---- the subset words of a block in compact form (ABI 5) ----------------------------------------------------------------
  * Between the two halves of a batched hash-range run every rank needs the OR of all ranks' subset words.  The dense row

@@ -32,6 +32,8 @@ YH_BATCH_MAX_SAMPLES = 256
 YH_PRESENCE_MAX_COVS = 16
 YH_EXPLAIN_BATCH_TILE = 2048
 YH_ABUND_BATCH_TILE = 1024
+YH_GATHER_ROUNDS_PER_SYNC = 32
+YH_GATHER_NOBODY = 0xFFFFFFFF  # an owner entry: no reference took the hash
 YH_LOOKUP_AUTO, YH_LOOKUP_STREAM, YH_LOOKUP_INDEXED = 0, 1, 2
 
 _ERR_NAMES = {
@@ -159,6 +161,10 @@ SIGNATURES = {
     "yh_explain_members_rows_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, C.c_uint32, _vp]),
     "yh_explain_batch_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp]),
     "yh_explain_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "yh_gather": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, _vp, C.POINTER(C.c_uint64),
+                            C.POINTER(C.c_int)]),
+    "yh_gather_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint64, _vp, C.POINTER(C.c_uint64),
+                                   C.POINTER(C.c_int)]),
     "yh_host_alloc": (C.c_int, [C.POINTER(_vp), C.c_uint64]),
     "yh_host_free": (C.c_int, [_vp]),
     "yh_db_nshared_device": (C.c_int, [_vp, _vp]),

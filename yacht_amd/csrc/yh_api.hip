@@ -2,6 +2,7 @@
 #include "yh_common.h"
 #include "yh_abund.h"
 #include "yh_explain.h"
+#include "yh_gather.h"
 #include "yh_sort.h"
 #include "yh_pack.h"
 
@@ -1318,6 +1319,60 @@ int yh_explain(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_
         }
     } while (0);
     yh_tfree(db, d_a); yh_tfree(db, d_bytes);
+    return rc;
+}
+
+// ---- the candidate references ranked by the sample hashes each adds (yh_gather.hip) ------------------------------
+int yh_gather_device(yh_db* db, const uint64_t* d_sample, const uint32_t* d_abund, uint64_t n_sample, const uint8_t* d_cand,
+                     uint32_t min_hits, yh_gather_row* d_rows, uint64_t cap_rows, uint32_t* d_owner, uint64_t* n_rows, int* more) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (!n_rows || !more) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+    if (min_hits == 0) { yh_set_error("min_hits must be at least 1"); return YH_ERR_INVALID_ARG; }
+    if (n_sample >> 32) { yh_set_error("yh_gather takes samples below 2^32 hashes"); return YH_ERR_INVALID_ARG; }
+    if ((n_sample && !d_sample) || (n_sample && db->n_refs && !d_cand) || (cap_rows && !d_rows)) {
+        yh_set_error("null device pointer");
+        return YH_ERR_INVALID_ARG;
+    }
+    YH_TRY(explain_supported(db));
+    YH_TRY(db_select(db));
+    YH_TRY(pipe_join(db));  // (no step context, batch slot or work list is read or written: nothing else to note)
+    fin_join(db);
+    return yh_q_gather(db, (const u64*)d_sample, d_abund, n_sample, d_cand, min_hits, d_rows, cap_rows, d_owner, (u64*)n_rows, more);
+}
+
+int yh_gather(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_t n_sample, const uint8_t* cand, uint32_t min_hits,
+              yh_gather_row* rows, uint64_t cap_rows, uint32_t* owner, uint64_t* n_rows, int* more) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    const u64 N = db->n_refs;
+    if (!n_rows || !more || (N && !cand) || (n_sample && !sample) || (cap_rows && !rows)) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+    if (min_hits == 0) { yh_set_error("min_hits must be at least 1"); return YH_ERR_INVALID_ARG; }
+    if (n_sample >> 32) { yh_set_error("yh_gather takes samples below 2^32 hashes"); return YH_ERR_INVALID_ARG; }
+    YH_TRY(explain_supported(db));
+    YH_TRY(db_select(db));
+    YH_TRY(upload_sample(db, sample, n_sample));
+    cap_rows = std::min<u64>(cap_rows, N);  // (a reference wins at most once)
+    u32 *d_a = nullptr, *d_owner = nullptr;
+    u8* d_bytes = nullptr;  // the rows, then the candidate table
+    const u64 off_cand = std::max<u64>(cap_rows, 1) * sizeof(yh_gather_row);
+    int rc = YH_OK;
+    do {
+        if ((abund && yh_tmalloc(db, (void**)&d_a, std::max<u64>(n_sample, 4) * sizeof(u32)) != hipSuccess) ||
+            (owner && yh_tmalloc(db, (void**)&d_owner, std::max<u64>(n_sample, 4) * sizeof(u32)) != hipSuccess) ||
+            yh_tmalloc(db, (void**)&d_bytes, off_cand + std::max<u64>(N, 16)) != hipSuccess) { yh_set_error("device allocation failed"); rc = YH_ERR_OOM; break; }
+        if ((abund && n_sample && hipMemcpyAsync(d_a, abund, n_sample * sizeof(u32), hipMemcpyHostToDevice, db->stream) != hipSuccess) ||
+            (N && hipMemcpyAsync(d_bytes + off_cand, cand, N, hipMemcpyHostToDevice, db->stream) != hipSuccess)) {
+            yh_set_error("gather upload failed"); rc = YH_ERR_HIP; break;
+        }
+        if ((rc = yh_gather_device(db, (const uint64_t*)db->d_sample_tmp, abund ? d_a : nullptr, n_sample, d_bytes + off_cand, min_hits,
+                                   (yh_gather_row*)d_bytes, cap_rows, d_owner, n_rows, more)) != YH_OK) break;
+        const bool down_ok = (!*n_rows || hipMemcpyAsync(rows, d_bytes, *n_rows * sizeof(yh_gather_row), hipMemcpyDeviceToHost, db->stream) == hipSuccess) &&
+                             (!owner || !n_sample || hipMemcpyAsync(owner, d_owner, n_sample * sizeof(u32), hipMemcpyDeviceToHost, db->stream) == hipSuccess);
+        if (!down_ok || hipStreamSynchronize(db->stream) != hipSuccess) {
+            yh_set_error("gather download failed: %s", hipGetErrorString(hipGetLastError()));
+            rc = YH_ERR_HIP;
+        }
+    } while (0);
+    yh_tfree(db, d_a); yh_tfree(db, d_owner); yh_tfree(db, d_bytes);
     return rc;
 }
 

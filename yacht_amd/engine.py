@@ -104,6 +104,34 @@ def check_member(member, n_refs: int) -> np.ndarray:
     return np.ascontiguousarray(member, dtype=np.uint8)
 
 
+# one row of RefDB.gather (include/yacht_hip.h: yh_gather_row)
+GATHER_ROW_DTYPE = np.dtype([("ref", np.uint32), ("n_overlap", np.uint32), ("n_unique", np.uint32), ("reserved_", np.uint32),
+                             ("w_unique", np.uint64)])
+
+
+def check_candidates(cand, n_refs: int) -> np.ndarray:
+    """The candidate table of RefDB.gather as uint8 [n_refs] of 0 / 1, or ValueError: one entry per reference, booleans or
+    integers (non-zero = candidate).  Host only: no library call."""
+    cand = np.asarray(cand)
+    if cand.ndim != 1 or cand.size != int(n_refs):
+        raise ValueError(f"cand must hold one entry per reference: {cand.size} entries for {int(n_refs)} references")
+    if cand.size and cand.dtype.kind not in "iub":
+        raise ValueError(f"candidate entries must be booleans or integers, not {cand.dtype}")
+    return np.ascontiguousarray(cand != 0, dtype=np.uint8)
+
+
+def check_gather_limits(min_hits, cap_rows, n_refs: int) -> Tuple[int, int]:
+    """(min_hits, cap_rows) of RefDB.gather as integers, or ValueError: min_hits in [1, 2**32 - 1], cap_rows None (no cap:
+    a reference wins at most once, so n_refs rows) or >= 0.  Host only: no library call."""
+    if int(min_hits) != min_hits or not 1 <= int(min_hits) <= 0xFFFFFFFF:
+        raise ValueError(f"min_hits must be an integer in [1, 2**32 - 1], not {min_hits}")
+    if cap_rows is None:
+        return int(min_hits), int(n_refs)
+    if int(cap_rows) != cap_rows or int(cap_rows) < 0:
+        raise ValueError(f"cap_rows must be None or an integer >= 0, not {cap_rows}")
+    return int(min_hits), min(int(cap_rows), int(n_refs))
+
+
 def check_members(members, n_samples: int, n_refs: int) -> np.ndarray:
     """The member rows of RefDB.explain_batch as uint8 [n_samples, n_refs], or ValueError: 1..256 samples, one row per
     sample, one byte per reference, each in [0, 127].  Host only: no library call."""
@@ -332,6 +360,37 @@ class RefDB:
         flags (0: none) and uint64 [8][2] totals out."""
         _lib.check(self._lib.yh_explain_device(self._h, C.c_void_p(d_sample), C.c_void_p(d_abund), n_sample, C.c_void_p(d_member),
                                                C.c_void_p(d_flags), C.c_void_p(d_totals)))
+
+    def gather(self, sample, cand, abund=None, min_hits: int = 1, cap_rows: Optional[int] = None, want_owner: bool = False):
+        """The candidates ranked by the sample hashes each adds (yh_gather): round after round the candidate holding the
+        most sample hashes nobody owns yet (ties: the smallest index) takes them.  cand: one byte per reference, non-zero =
+        candidate.  abund: one abundance per sample hash, or None (all 1).  cap_rows: at most this many rows (None: no
+        cap).  Returns (rows, more, owner): rows a structured array (GATHER_ROW_DTYPE: ref, n_overlap, n_unique, w_unique),
+        more True when the cap cut the run short of a candidate with min_hits live hashes, owner uint32 [n] with
+        0xFFFFFFFF = nobody (None without want_owner)."""
+        if abund is None:
+            sample = _as_u64(sample)
+        else:
+            sample, abund = check_abundances(sample, abund)
+        cand = check_candidates(cand, self.n_refs)
+        min_hits, cap = check_gather_limits(min_hits, cap_rows, self.n_refs)
+        rows = np.zeros(max(cap, 1), dtype=GATHER_ROW_DTYPE)
+        owner = np.full(sample.size, _lib.YH_GATHER_NOBODY, dtype=np.uint32) if want_owner else None
+        n_rows, more = C.c_uint64(0), C.c_int(0)
+        _lib.check(self._lib.yh_gather(self._h, _ptr(sample), _ptr(abund), sample.size, _ptr(cand), min_hits, _ptr(rows), cap,
+                                       _ptr(owner), C.byref(n_rows), C.byref(more)))
+        return rows[:int(n_rows.value)].copy(), bool(more.value), owner
+
+    def gather_device(self, d_sample: int, d_abund: int, n_sample: int, d_cand: int, min_hits: int, d_rows: int, cap_rows: int,
+                      d_owner: int = 0) -> Tuple[int, bool]:
+        """yh_gather_device: uint64 sample, uint32 abundances (0: all 1) and uint8 [N] candidate table in, cap_rows rows
+        of GATHER_ROW_DTYPE and (d_owner != 0) uint32 [n_sample] owners out.  Synchronizes the handle's stream once per
+        chunk of rounds.  Returns (n_rows, more)."""
+        n_rows, more = C.c_uint64(0), C.c_int(0)
+        _lib.check(self._lib.yh_gather_device(self._h, C.c_void_p(d_sample), C.c_void_p(d_abund), n_sample, C.c_void_p(d_cand),
+                                              int(min_hits), C.c_void_p(d_rows), int(cap_rows), C.c_void_p(d_owner),
+                                              C.byref(n_rows), C.byref(more)))
+        return int(n_rows.value), bool(more.value)
 
     def explain_batch(self, samples: Sequence[np.ndarray], members, abunds=None, want_flags: bool = True):
         """explain for a block of 1..256 samples, each with its own member row, in one lookup launch (yh_explain_batch).

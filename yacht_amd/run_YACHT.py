@@ -59,6 +59,14 @@ ARGUMENTS = (
     ("--residual_coverage", dict(type=float, default=None,
                                  help="The --min_coverage_list value whose call set results/residual.sig.zip is taken for "
                                       "(with --residual; default: the smallest value of the list).")),
+    ("--gather", dict(action="store_true",
+                      help="Also rank the organisms called present by the sample hashes each adds, a minimum set cover as "
+                           "`sourmash gather` makes it: results/gather_profile.tsv (per min_coverage and rank: the organism, the "
+                           "sample hashes it holds, those no higher-ranked organism took, and their abundance).  One sample file.")),
+    ("--gather_min_hits", dict(type=int, default=1,
+                               help="Stop the ranking when the best remaining organism adds fewer sample hashes than this (with --gather).")),
+    ("--gather_coverage", dict(type=float, nargs="+", default=None,
+                               help="The --min_coverage_list values the ranking is made for (with --gather; default: all of them).")),
 )
 
 # messages the reference raises with (callers and its tests match on them)
@@ -147,6 +155,11 @@ def main(args) -> None:
         from . import residual
 
         residual_cov = residual.residual_coverage(args)  # (ValueError before anything is written or any device work)
+    gather_plan = None
+    if getattr(args, "gather", False) or getattr(args, "gather_coverage", None) is not None:
+        from . import gather
+
+        gather_plan = gather.gather_options(args, len(files))  # (ValueError before anything is written or any device work)
     if len(files) > 1:
         from . import cohort
 
@@ -212,6 +225,15 @@ def main(args) -> None:
             call_sets = residual.call_sets_of(manifest["organism_name"], results if has_raw else results[1:])
             explained = residual.explain_call_sets(hr._LAST_RUN["db"], hr._LAST_RUN["mins"],
                                                    residual.sample_abundances_or_none(sample_sig), call_sets)
+    if gather_plan is not None:  # one call per chosen coverage on the still-resident database
+        from . import residual as _residual  # (the call sets and the sample's abundances are made as for --residual)
+
+        with phases.phase("gather"):
+            all_covs = [float(c) for c in (covs if has_raw else covs[1:])]
+            all_sets = _residual.call_sets_of(manifest["organism_name"], results if has_raw else results[1:])
+            gather_sets = [all_sets[all_covs.index(c)] for c in gather_plan[0]]
+            gather_rows = gather.gather_call_sets(hr._LAST_RUN["db"], hr._LAST_RUN["mins"],
+                                                  _residual.sample_abundances_or_none(sample_sig), gather_sets, gather_plan[1])
     hr.release_reference_dbs()
     results = trim_results(results)
 
@@ -223,6 +245,8 @@ def main(args) -> None:
         abundance.write_profile(results if has_raw else results[1:], covs if has_raw else covs[1:], results_folder)
     if want_residual:
         residual.write_outputs(results_folder, sample_sig, user_covs, call_sets, *explained, residual_cov)
+    if gather_plan is not None:
+        gather.write_profile(results_folder, sample_sig, gather_plan[0], gather_rows, manifest["organism_name"])
     _t_write.__exit__(None, None, None)
 
 
