@@ -300,6 +300,7 @@ int yh_run_device_join(yh_db* db);
  *   yh_explain_batch / yh_explain_batch_device,              | yes (no step state is read or written) | yes
  *     yh_explain_members_rows_device                         |                                       |
  *   yh_gather / yh_gather_device                             | yes (no step state is read or written) | yes
+ *   yh_gather_batch / yh_gather_batch_device                 | yes (no step state is read or written) | yes
  *   yh_db_set_stream                                         | yes (drains the old stream first)      | yes
  *   (*) the CURRENT context = the one named by the last yh_run_local*_device / yh_run_finish*_device call (0 at start).
  * Every query entry point first completes the pending stages of pipelined steps (yh_run_device_join) by itself.          */
@@ -567,7 +568,7 @@ int yh_explain_batch(yh_db* db, const uint64_t* samples, const uint64_t* sample_
  * ordering (YH_ERR_UNSORTED), uploads, runs and downloads.
  * YH_ERR_UNSUPPORTED exactly where yh_explain returns it: a handle without the directory or the index (YH_DB_NO_DIRECTORY,
  * YH_DB_NO_INDEX, YH_DB_PAIRWISE_ONLY), or with ghosts registered (yh_db_set_ghosts).
- * Nothing is built for shards or for blocks of samples.
+ * Nothing is built for shards; a block of samples has yh_gather_batch_device below.
  * (No reference counterpart: its use-case scripts subtract sketches with Python sets.)                                        */
 typedef struct yh_gather_row {
     uint32_t ref, n_overlap, n_unique, reserved_;
@@ -581,6 +582,50 @@ int yh_gather_device(yh_db* db, const uint64_t* d_sample, const uint32_t* d_abun
                      uint32_t* d_owner /* [n_sample] or NULL */, uint64_t* n_rows /* HOST */, int* more /* HOST */);
 int yh_gather(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_t n_sample, const uint8_t* cand,
               uint32_t min_hits, yh_gather_row* rows, uint64_t cap_rows, uint32_t* owner, uint64_t* n_rows, int* more);
+
+/* ---- the same ranking for a BLOCK of samples, each with its own candidates (additive in ABI 8) ---------------------------------
+ * The single call is launch-bound: two small launches per row with the device almost idle.  This ranks 1..YH_BATCH_MAX_SAMPLES
+ * samples in the same launches.  The block is laid out exactly as for yh_explain_batch_device: samples back to back, strictly
+ * ascending inside each sample, device offsets [n_samples + 1], and total_hashes (< 2^32) as the caller's copy of
+ * d_sample_offsets[n_samples] that only sizes launches and buffers (the offsets must ascend and stay inside d_samples, d_abund
+ * and d_owner, and total_hashes must not be below the last offset: they are not checked).  Reference j is a candidate of
+ * sample s when d_members[s * N + j] & cand_mask is non-zero, so the member rows yh_explain_members_rows_device writes are the
+ * candidate tables of up to seven call sets: one call per set, cand_mask = 1 << k, ranks set k, and nothing new is uploaded.
+ * Contract: for every sample s,
+ *   d_n_rows[s], d_more[s], the first d_n_rows[s] rows of d_rows + s * cap_rows, and d_owner[off[s] .. off[s + 1])
+ * are bit-identical to what yh_gather_device returns for that sample alone with the candidate table (member & cand_mask) != 0
+ * and the same min_hits and cap_rows.  Rows behind d_n_rows[s] are not written.  Every d_n_rows[s] and d_more[s] of the first
+ * n_samples is written by every call: nothing of an earlier, larger block survives.  An empty database or total_hashes == 0:
+ * zero rows, more 0 and all total_hashes owners "nobody" (so with total_hashes == 0 no owner is written, whatever the device
+ * offsets say).  d_owner may be NULL.
+ * How it runs: one clear, one lookup launch (a workgroup takes a tile of consecutive hashes of one sample, in
+ * yh_explain_batch_device's tile order), one init, then per round exactly two launches whatever n_samples is -- a pick with
+ * a workgroup per sample and a claim over the live lists of the samples still running -- and the kernel boundary is the only
+ * ordering between workgroups.  Working memory is dense, about 21 bytes per (sample, reference) cell plus 8 per hash, from
+ * the handle's buffer cache (YH_ERR_OOM when it cannot be had).
+ * d_n_rows and d_more are DEVICE arrays and the device form DOES NOT synchronize the host: it enqueues min(cap_rows, N) + 1
+ * rounds, and the kernels of a round leave at once when their sample, or the whole block, is done.  That is what bounds
+ * cap_rows: at most YH_GATHER_BATCH_MAX_ROWS.  It reads no step context, batch slot or work list (interleaving table above:
+ * yes / yes), completes pending pipelined stages first, and waits for a finish stream's rows like
+ * yh_explain_members_rows_device.
+ * YH_ERR_INVALID_ARG: n_samples == 0 or > YH_BATCH_MAX_SAMPLES, min_hits == 0, cand_mask == 0, cap_rows >
+ * YH_GATHER_BATCH_MAX_ROWS, total_hashes >= 2^32.  YH_ERR_UNSUPPORTED exactly where yh_gather_device returns it.
+ * yh_gather_batch is the synchronous host form (total = sample_offsets[n_samples]): it validates every sample's ordering
+ * (YH_ERR_UNSORTED), then uploads, runs and downloads; rows [n_samples][cap_rows] (only the first n_rows[s] of a sample are
+ * written), owner [total] or NULL, n_rows and more [n_samples].                                                              */
+#define YH_GATHER_BATCH_MAX_ROWS 4096
+#ifndef YH_GATHER_BATCH_TILE
+#define YH_GATHER_BATCH_TILE 1024 /* consecutive hashes of one sample a lookup workgroup takes */
+#endif
+int yh_gather_batch_device(yh_db* db, const uint64_t* d_samples, const uint64_t* d_sample_offsets /* [n_samples + 1] */,
+                           const uint32_t* d_abund /* [total_hashes] or NULL: all 1 */, uint32_t n_samples, uint64_t total_hashes,
+                           const uint8_t* d_members /* [n_samples][N] */, uint8_t cand_mask, uint32_t min_hits,
+                           yh_gather_row* d_rows /* [n_samples][cap_rows] */, uint64_t cap_rows,
+                           uint32_t* d_owner /* [total_hashes] or NULL */,
+                           uint32_t* d_n_rows /* [n_samples], DEVICE */, uint8_t* d_more /* [n_samples], DEVICE */);
+int yh_gather_batch(yh_db* db, const uint64_t* samples, const uint64_t* sample_offsets, const uint32_t* abund, uint32_t n_samples,
+                    const uint8_t* members, uint8_t cand_mask, uint32_t min_hits, yh_gather_row* rows, uint64_t cap_rows,
+                    uint32_t* owner, uint32_t* n_rows, uint8_t* more);
 
 /* ---- the subset words of a block in compact form (ABI 5) ----------------------------------------------------------------
  * Between the two halves of a batched hash-range run every rank needs the OR of all ranks' subset words.  The dense row

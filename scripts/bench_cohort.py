@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """`yacht run` over a cohort (yacht_amd/cohort.py) end to end, on a synthetic database with real-shape samples.
 
-    python scripts/bench_cohort.py [--n-refs 85205] [--samples 1024] [--single 32] [--residual] [--abundance] [--commit ID] [--out FILE]
+    python scripts/bench_cohort.py [--n-refs 85205] [--samples 1024] [--single 32] [--residual] [--abundance] [--gather --gather_top K] [--commit ID] [--out FILE]
 
 Prints one JSON line: samples/s of the cohort command with its phase split (yacht_amd/cohort.py main: check, db, table,
 device_setup, parse_wait, device_wait, the device time of uploads / batch counts + compact rows / presence kernel, d2h,
 assemble, writes), the presence kernel alone against yh_hyp_test (host) over the same rows, and `--single` of the samples
 through the single-sample command in the same process (warm) for comparison.  --residual runs the cohort (and the single
 commands) with `yacht run --residual`: gpu_explain is then the phase of the residual's device work.  --abundance runs them with `yacht run --abundance`: gpu_abund is
-the device time of the blocks' depth passes (YACHT_COHORT_ABUND=loop in the environment: the per-sample loop).  --commit is
+the device time of the blocks' depth passes (YACHT_COHORT_ABUND=loop in the environment: the per-sample loop).  --gather
+--gather_top K runs them with `yacht run --gather --gather_top K`: gpu_gather is the device time of the blocks' rankings
+(YACHT_COHORT_GATHER=loop in the environment: the host wall time of one host-form call per sample and coverage).  --commit is
 recorded."""
 from __future__ import annotations
 
@@ -131,6 +133,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1002)
     ap.add_argument("--residual", action="store_true")
     ap.add_argument("--abundance", action="store_true")
+    ap.add_argument("--gather", action="store_true")
+    ap.add_argument("--gather_top", type=int, default=None)
     ap.add_argument("--commit", default="")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -145,7 +149,7 @@ def main():
     os.makedirs(out)
     args = SimpleNamespace(json=cfg, sample_file=paths, significance=0.99, num_threads=a.threads, keep_raw=False, show_all=False,
                            min_coverage_list=COVS, outdir=out, residual=a.residual, residual_coverage=None,
-                           abundance=a.abundance)
+                           abundance=a.abundance, gather=a.gather, gather_top=a.gather_top, gather_min_hits=1, gather_coverage=None)
     t0 = time.perf_counter()
     phases = cohort.main(args, paths)
     wall = time.perf_counter() - t0
@@ -170,6 +174,9 @@ def main():
         "residual": bool(a.residual),
         "abundance": bool(a.abundance),
         "cohort_abund": os.environ.get("YACHT_COHORT_ABUND", ""),
+        "gather": bool(a.gather),
+        "gather_top": a.gather_top,
+        "cohort_gather": os.environ.get("YACHT_COHORT_GATHER", ""),
         "setup_s": round(setup_s, 1),
         "bottleneck": None,
         "cohort": {"samples": a.samples, "wall_s": round(wall, 2), "samples_per_s": round(a.samples / wall, 2),

@@ -17,7 +17,18 @@ and a 10^6-hash sample (synth.sample_device) -- with the references that overlap
   * the wall time of tests/gather_oracle.py's gather_oracle (numpy, one host core) on the same input, after its rows and
     owners were compared with the device's.
 The pass-A and abundance calls rotate through four samples and alternate inside each of `rounds` rounds; the median round is
-reported with the spread.  Prints one JSON line and writes it to --out (default profiles/gather/bench_gather.json)."""
+reported with the spread.  Prints one JSON line and writes it to --out (default profiles/gather/bench_gather.json).
+
+    python scripts/bench_gather.py --batch [--n-refs 85205] [--rounds 3] [--batch-caps 64 1024] [--skip-loop] [--out FILE]
+
+--batch times ONE yh_gather_batch_device over a resident block against a LOOP of the unchanged yh_gather_device over the same
+block: the same samples, abundances and candidates (the references that overlap each sample, as bit 0 of the member rows),
+min_hits 1, no owners.  Blocks: 256 real-shape 83 k-hash samples, and 32 samples of 10^6 hashes; cap_rows 64 and 1024.
+Both are timed with the host clock from the first call to the end of a synchronize -- the looped call synchronizes the host
+itself, so that is what a caller of either waits for -- and reported in us per sample: the median of `rounds` rounds with the
+spread.  Before anything is timed every sample's count, `more` and rows must equal the looped call's.  --skip-loop runs the
+batched calls alone (for a kernel trace: profiles/gather/kernel_stats_batch.txt).  Default --out:
+profiles/gather/bench_gather_batch.json."""
 from __future__ import annotations
 
 import argparse
@@ -40,6 +51,102 @@ from yacht_amd.engine import RefDB  # noqa: E402
 N_ROTATE = 4
 
 
+def batch_main(args) -> None:
+    import torch
+
+    assert _lib.device_count() >= 1, "bench_gather.py needs an MI355X"
+    dev = torch.device("cuda:0")
+    N = args.n_refs
+    values, offsets, _ = synth.config3_device(seed=1002, n_refs=N, n_sample=1000, device="cuda:0")
+    torch.cuda.synchronize()
+    db = RefDB.from_device(values.data_ptr(), offsets.data_ptr(), N)
+    stream = torch.cuda.Stream()
+    db.set_stream(stream.cuda_stream)
+    g = torch.Generator(device=dev)
+    g.manual_seed(5)
+    result = {"bench": "gather_batch", "n_refs": N, "n_hashes_db": int(values.numel()), "rounds": args.rounds, "min_hits": 1,
+              "owners": False, "clock": "host, first call to the end of a synchronize", "loop_skipped": bool(args.skip_loop), "blocks": {}}
+    ok = True
+    for name, shape, n_sample, b in (("256_real_shape_83k", "real", 83_000, 256), ("32_of_1e6_hashes", "present", 1_000_000, 32)):
+        b = min(b, args.batch_samples) if args.batch_samples else b
+        samples = [synth.sample_device(values, offsets, seed=900 + i, n_sample=n_sample, shape=shape) for i in range(b)]
+        sizes = [int(s.numel()) for s in samples]
+        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        total = int(offs[-1])
+        d_s = torch.cat(samples)
+        d_o = torch.from_numpy(offs).to(dev)
+        d_a = torch.randint(1, 1001, (total,), generator=g, device=dev, dtype=torch.int32)
+        members = torch.zeros((b, N), dtype=torch.uint8, device=dev)
+        cnt = [torch.zeros(N, dtype=torch.int32, device=dev) for _ in range(3)]
+        for i in range(b):  # the candidates of sample i: the references that overlap it
+            db.run_indexed_device(samples[i].data_ptr(), sizes[i], cnt[0].data_ptr(), cnt[1].data_ptr(), cnt[2].data_ptr())
+            db.synchronize()
+            members[i] = (cnt[0] > 0).to(torch.uint8)
+        torch.cuda.synchronize()
+        block = {"samples": b, "total_hashes": total, "candidates_mean": round(float(members.sum()) / b, 1), "caps": {}}
+        for cap in args.batch_caps:
+            rows_b = torch.zeros((b, cap, 3), dtype=torch.int64, device=dev)
+            rows_l = torch.zeros((b, cap, 3), dtype=torch.int64, device=dev)
+            n_b = torch.zeros(b, dtype=torch.int32, device=dev)
+            more_b = torch.zeros(b, dtype=torch.uint8, device=dev)
+
+            def batched():
+                t0 = time.perf_counter()
+                db.gather_batch_device(d_s.data_ptr(), d_o.data_ptr(), d_a.data_ptr(), b, total, members.data_ptr(), 1, 1, rows_b.data_ptr(),
+                                       cap, 0, n_b.data_ptr(), more_b.data_ptr())
+                db.synchronize()
+                return (time.perf_counter() - t0) * 1e6 / b
+
+            def looped():
+                got = []
+                t0 = time.perf_counter()
+                for i in range(b):
+                    got.append(db.gather_device(d_s.data_ptr() + 8 * int(offs[i]), d_a.data_ptr() + 4 * int(offs[i]), sizes[i],
+                                                members[i].data_ptr(), 1, rows_l[i].data_ptr(), cap, 0))
+                db.synchronize()
+                return (time.perf_counter() - t0) * 1e6 / b, got
+
+            out = {}
+            with torch.cuda.stream(stream):
+                batched()  # (warm: the working memory comes from the buffer cache afterwards)
+                if not args.skip_loop:
+                    _, got = looped()
+                    torch.cuda.synchronize()
+                    n_rows, more = n_b.cpu().numpy(), more_b.cpu().numpy()
+                    assert [int(x) for x in n_rows] == [k for k, _ in got] and [bool(x) for x in more] == [m for _, m in got], (name, cap)
+                    hb, hl = rows_b.cpu().numpy(), rows_l.cpu().numpy()
+                    assert all(np.array_equal(hb[i, :k], hl[i, :k]) for i, (k, _) in enumerate(got)), (name, cap)
+                    out["rows_equal_the_looped_calls"] = True
+                    out["rows_mean"] = round(float(n_rows.mean()), 1)
+                    out["samples_cut_at_the_cap"] = int(more.sum())
+                tb = [batched() for _ in range(args.rounds)]
+                tl = [looped()[0] for _ in range(args.rounds)] if not args.skip_loop else []
+            out["batched_us_per_sample"] = round(float(np.median(tb)), 2)
+            out["batched_rounds_us_per_sample"] = [round(x, 2) for x in tb]
+            out["rounds_enqueued"] = min(cap, N) + 1
+            if tl:
+                out["looped_us_per_sample"] = round(float(np.median(tl)), 2)
+                out["looped_rounds_us_per_sample"] = [round(x, 2) for x in tl]
+                out["looped_over_batched"] = round(out["looped_us_per_sample"] / out["batched_us_per_sample"], 2)
+                out["batched_no_slower"] = out["batched_us_per_sample"] <= out["looped_us_per_sample"]
+                ok = ok and out["batched_no_slower"]
+            else:
+                out["looped_us_per_sample"] = None  # unmeasured: --skip-loop
+            block["caps"][str(cap)] = out
+            del rows_b, rows_l
+        result["blocks"][name] = block
+        del samples, d_s, d_a, members
+    result["accepted"] = None if args.skip_loop else ok
+    db.close()
+    line = json.dumps(result)
+    print(line)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
+    if not args.skip_loop and not ok:
+        sys.exit("batched us per sample above looped us per sample")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--n-refs", type=int, default=85_205)
@@ -47,8 +154,16 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--skip-oracle", action="store_true", help="no host oracle and no comparison with it (for a profiler run)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gather", "bench_gather.json"))
+    ap.add_argument("--batch", action="store_true", help="yh_gather_batch_device against a loop of yh_gather_device")
+    ap.add_argument("--batch-caps", type=int, nargs="+", default=[64, 1024])
+    ap.add_argument("--batch-samples", type=int, default=0, help="at most this many samples per block (0: 256 and 32)")
+    ap.add_argument("--skip-loop", action="store_true", help="--batch: the batched calls alone (for a profiler run)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "gather", "bench_gather_batch.json" if args.batch else "bench_gather.json")
+    if args.batch:
+        return batch_main(args)
     import torch
 
     assert _lib.device_count() >= 1, "bench_gather.py needs an MI355X"

@@ -8,6 +8,9 @@ over n = 0..max reference size gives their table, gathered on the host by n_cov.
 assembles block j - 1's tables (the single path's own helpers: coverage_frame, trim_results), host threads parse block
 j + 1, and a pool of --num_threads processes writes the tables.
 
+With --gather --gather_top K the block's ranking follows on the device (yh_explain_members_rows_device, then one
+yh_gather_batch_device per gather coverage): results/<stem>/gather_profile.tsv and results/cohort_gather.tsv.
+
 Output: results/<stem>/ per sample with overlap (what a single-sample run of that file writes into results/),
 results/cohort_samples.tsv and results/cohort_presence.tsv.  Every input is checked before any device work; the
 per-sample intermediate files of the single path (multisearch CSV, list files) are not written.  Every sample is parsed
@@ -91,6 +94,10 @@ def check_inputs(args, files: List[str]) -> dict:
         from . import residual
 
         residual.residual_coverage(args)
+    if any(getattr(args, k, None) for k in ("gather", "gather_coverage", "gather_top")):
+        from . import gather
+
+        gather.gather_options(args, len(files))
     json_file_path = str(Path(args.json).absolute())
     paths = [str(Path(f).absolute()) for f in files]
     outdir = str(Path(args.outdir).absolute())
@@ -130,7 +137,8 @@ def check_inputs(args, files: List[str]) -> dict:
     return dict(config=config, paths=paths, outdir=outdir, meta=meta)
 
 
-def _write_one(folder: str, results, covs, has_raw: bool, keep_raw: bool, show_all: bool, profile: bool = False, explained=None) -> None:
+def _write_one(folder: str, results, covs, has_raw: bool, keep_raw: bool, show_all: bool, profile: bool = False, explained=None,
+               ranked=None) -> None:
     os.makedirs(folder, exist_ok=True)
     ry.write_sample_results(results, covs, has_raw, folder, keep_raw, show_all)
     if profile:
@@ -142,17 +150,25 @@ def _write_one(folder: str, results, covs, has_raw: bool, keep_raw: bool, show_a
 
         sig, call_sets, flags, totals, cov = explained
         residual.write_outputs(folder, sig, covs if has_raw else covs[1:], call_sets, flags, totals, cov)
+    if ranked is not None:  # the sample's gather_profile.tsv frame of --gather
+        from . import gather
+
+        gather.write_frame(folder, ranked)
 
 
 class _Device:
     """The device side of a cohort run: the block's buffers and the calls of one block."""
 
     def __init__(self, db, covs, ksize: int, ani_thresh: float, thr_table: np.ndarray, cap: int = 0, abund_samples: int = 0,
-                 residual_sets: int = 0):
+                 residual_sets: int = 0, gather_sets=(), gather_min_hits: int = 1, gather_top: int = 0, n_user: int = 0,
+                 max_samples: int = BLOCK):
         """cap: compact rows a block may have before it takes the dense rows (0: BLOCK * N, at most 2^20; grows after a
         block that exceeded it).  abund_samples (--abundance): samples of the largest block; 0 = no abundance pass.
         residual_sets (--residual): the number of user coverages, the LAST residual_sets entries of covs, whose call sets
-        the block's explain passes answer, seven per pass; 0 = no explain pass."""
+        the block's explain passes answer, seven per pass; 0 = no explain pass.  gather_sets (--gather): which of the n_user
+        user coverages (indices into them; they are the LAST n_user entries of covs) the block's ranking is made for, with
+        gather_min_hits and at most gather_top rows per sample and coverage, for blocks of up to max_samples; empty = no
+        ranking."""
         import torch
 
         self.torch = torch
@@ -178,11 +194,22 @@ class _Device:
             self.abund_rows = None
             self.ev_abund = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         self.residual_sets = int(residual_sets)
-        if self.residual_sets > 0:  # per block: member rows [BLOCK][N], and per pass of seven call sets totals and flags
+        self.gather_sets = [int(g) for g in gather_sets]
+        self.d_x_abund = None
+        if self.residual_sets > 0 or self.gather_sets:  # member rows [BLOCK][N] of up to seven call sets at a time
+            self.members = torch.zeros((BLOCK, max(N, 1)), dtype=torch.uint8, device=self.dev)
+        if self.gather_sets:  # per block and gather coverage: rows [samples][top], their counts and `more` bytes
+            self.n_user = int(n_user)
+            self.gather_min_hits, self.gather_top = int(gather_min_hits), int(gather_top)
+            g, bmax = len(self.gather_sets), max(1, min(BLOCK, int(max_samples)))
+            self.g_rows = torch.zeros((g, bmax, self.gather_top, 3), dtype=torch.int64, device=self.dev)
+            self.g_n = torch.zeros((g, bmax), dtype=torch.int32, device=self.dev)
+            self.g_more = torch.zeros((g, bmax), dtype=torch.uint8, device=self.dev)
+            self.ev_gather = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        if self.residual_sets > 0:  # per block and pass of seven call sets: totals and flags
             if self.residual_sets > self.covs.size:
                 raise ValueError(f"{self.residual_sets} call sets for {self.covs.size} coverages")
             self.x_passes = (self.residual_sets + MAX_SETS - 1) // MAX_SETS
-            self.members = torch.zeros((BLOCK, max(N, 1)), dtype=torch.uint8, device=self.dev)
             self.x_totals = torch.zeros((self.x_passes, BLOCK, 8, 2), dtype=torch.int64, device=self.dev)
             self.x_flags = None  # [passes][the block's hashes], made per block
             self.d_x_abund = None
@@ -248,6 +275,37 @@ class _Device:
             self.db.explain_batch_device(self.d_samples.data_ptr(), self.d_offs.data_ptr(), d_abund, b, total,
                                          self.members.data_ptr(), self.x_flags[p].data_ptr(), self.x_totals[p].data_ptr())
 
+    def gather_pass(self, rows, d_n_rows: int, cap: int, out, b: int, total: int) -> None:
+        """The block's ranking: per pass of up to seven user coverages that holds a gather coverage, the samples' member rows
+        from the rows' present bytes (yh_explain_members_rows_device), then one yh_gather_batch_device per gather coverage
+        with that coverage's bit as cand_mask.  No host sync: the counts and `more` bytes stay on the device."""
+        first = self.covs.size - self.n_user  # (the forced 1.0 in front is no user coverage)
+        d_abund = self.d_x_abund.data_ptr() if self.d_x_abund is not None else 0
+        for c0 in range(0, self.n_user, MAX_SETS):
+            mine = [(g, u - c0) for g, u in enumerate(self.gather_sets) if c0 <= u < c0 + MAX_SETS]
+            if not mine:
+                continue
+            self.db.explain_members_rows_device(rows.data_ptr(), d_n_rows, cap, out[1][first + c0].data_ptr(),
+                                                min(MAX_SETS, self.n_user - c0), b, self.members.data_ptr())
+            for g, bit in mine:
+                self.db.gather_batch_device(self.d_samples.data_ptr(), self.d_offs.data_ptr(), d_abund, b, total, self.members.data_ptr(),
+                                            1 << bit, self.gather_min_hits, self.g_rows[g].data_ptr(), self.gather_top, 0,
+                                            self.g_n[g].data_ptr(), self.g_more[g].data_ptr())
+
+    def _upload_sketch_abundances(self, mins, abunds, explain_abunds, total: int) -> None:
+        """d_x_abund for the explain and gather passes: the block's abundances where the sketches track them (a sample
+        without counts every hash once), None when no sample of the block does.  Once per block."""
+        t = self.torch
+        if self.d_x_abund is not None or self._x_abund_done:
+            return
+        self._x_abund_done = True
+        if abunds is not None:
+            self.d_x_abund = self.d_abund
+        elif explain_abunds is not None and total and any(a is not None for a in explain_abunds):
+            cat_ab = np.concatenate([np.ones(m.size, np.uint32) if a is None else np.ascontiguousarray(a, dtype=np.uint32)
+                                     for m, a in zip(mins, explain_abunds)]).view(np.int32)
+            self.d_x_abund = t.from_numpy(cat_ab).pin_memory().to(self.dev, non_blocking=True)
+
     def launch(self, mins: List[np.ndarray], abunds=None, explain_abunds=None) -> int:
         """Queue one block: upload, batch counts, compact rows, presence test, row count to the host.  No host sync.
         abunds (--abundance): every sample's abundances.  explain_abunds (the explain pass without --abundance): per sample
@@ -279,20 +337,20 @@ class _Device:
             self.ev_abund[0].record()
             self.abundance_pass(offs, b)
             self.ev_abund[1].record()
+        total = int(offs[-1])
+        self.x_block = (b, total)
+        self.d_x_abund, self._x_abund_done = None, False
         if self.residual_sets > 0:
-            total = int(offs[-1])
-            self.x_block = (b, total)
             self.x_flags = t.empty((self.x_passes, max(total, 1)), dtype=t.uint8, device=self.dev)
-            self.d_x_abund = None
             self.ev_explain[0].record()  # (the upload of a mixed cohort's abundances below belongs to the pass)
-            if abunds is not None:
-                self.d_x_abund = self.d_abund
-            elif explain_abunds is not None and total and any(a is not None for a in explain_abunds):
-                cat_ab = np.concatenate([np.ones(m.size, np.uint32) if a is None else np.ascontiguousarray(a, dtype=np.uint32)
-                                         for m, a in zip(mins, explain_abunds)]).view(np.int32)
-                self.d_x_abund = t.from_numpy(cat_ab).pin_memory().to(self.dev, non_blocking=True)
+            self._upload_sketch_abundances(mins, abunds, explain_abunds, total)
             self.explain_pass(self.rows, self.n_rows[1].data_ptr(), self.cap, self.out, b, total)
             self.ev_explain[1].record()
+        if self.gather_sets:
+            self.ev_gather[0].record()  # (likewise, when no explain pass uploaded them)
+            self._upload_sketch_abundances(mins, abunds, explain_abunds, total)
+            self.gather_pass(self.rows, self.n_rows[1].data_ptr(), self.cap, self.out, b, total)
+            self.ev_gather[1].record()
         self.n_rows_host.copy_(self.n_rows, non_blocking=True)
         return b
 
@@ -311,6 +369,8 @@ class _Device:
             timer["gpu_abund"] += self.ev_abund[0].elapsed_time(self.ev_abund[1]) / 1e3
         if self.residual_sets > 0:
             timer["gpu_explain"] += self.ev_explain[0].elapsed_time(self.ev_explain[1]) / 1e3
+        if self.gather_sets:
+            timer["gpu_gather"] += self.ev_gather[0].elapsed_time(self.ev_gather[1]) / 1e3
         k = int(self.n_rows_host[0])
         rows, out = self.rows, self.out
         abund_rows = self.abund_rows if self.abund is not None else None
@@ -332,6 +392,10 @@ class _Device:
                 self.ev_explain[0].record()
                 self.explain_pass(rows, d_k.data_ptr(), k, out, b, self.x_block[1])
                 self.ev_explain[1].record()
+            if self.gather_sets:  # (and the ranking's candidates)
+                self.ev_gather[0].record()
+                self.gather_pass(rows, d_k.data_ptr(), k, out, b, self.x_block[1])
+                self.ev_gather[1].record()
             t0 = time.perf_counter()
             t.cuda.synchronize(self.dev)
             timer["device_wait"] += time.perf_counter() - t0
@@ -339,6 +403,8 @@ class _Device:
             timer["gpu_presence"] += ev[1].elapsed_time(ev[2]) / 1e3
             if self.residual_sets > 0:
                 timer["gpu_explain"] += self.ev_explain[0].elapsed_time(self.ev_explain[1]) / 1e3
+            if self.gather_sets:
+                timer["gpu_gather"] += self.ev_gather[0].elapsed_time(self.ev_gather[1]) / 1e3
             timer["dense_fallback_blocks"] += 1
             self._alloc(int(k * 1.25) + 1)  # (the next blocks: compact rows again)
         t0 = time.perf_counter()
@@ -349,6 +415,13 @@ class _Device:
                      abund_rows[2][:k].cpu().numpy()),)
         if self.residual_sets > 0:  # flags [passes][the block's hashes], totals [passes][b][8][2]
             got += ((self.x_flags[:, :self.x_block[1]].cpu().numpy(), self.x_totals[:, :b].cpu().numpy().view(np.uint64)),)
+        if self.gather_sets:  # counts [gather coverages][b] and rows [gather coverages][b][the longest ranking]
+            from .engine import GATHER_ROW_DTYPE
+
+            g_n = self.g_n[:, :b].cpu().numpy().view(np.uint32)
+            longest = int(g_n.max()) if g_n.size else 0
+            g_rows = self.g_rows[:, :b, :longest].contiguous().cpu().numpy().reshape(len(self.gather_sets), b, longest * 3)
+            got += ((g_rows.view(GATHER_ROW_DTYPE), g_n),)
         timer["d2h"] += time.perf_counter() - t0
         return got
 
@@ -361,10 +434,12 @@ def main(args, files: List[str]) -> dict:
     the presence kernel), gpu_abund (with --abundance: the block's yh_abund_batch_device call -- its yh_abund_device calls under
     YACHT_COHORT_ABUND=loop -- and the gather of their values at the compact rows), gpu_explain (with --residual: device time of the block's member-row and batched explain passes, plus
     the wall time of the host-form yh_explain calls of samples whose tables the host recomputed, or of every sample under
-    YACHT_COHORT_EXPLAIN=host), d2h, assemble, writes (what the write pool had left after the last block), cohort_files (the two
+    YACHT_COHORT_EXPLAIN=host), gpu_gather (with --gather: device time of the block's member-row passes and batched rankings, plus
+    the wall time of the host-form yh_gather calls of samples whose tables the host recomputed, or of every sample under
+    YACHT_COHORT_GATHER=loop), d2h, assemble, writes (what the write pool had left after the last block), cohort_files (the two
     cohort tables), total."""
     timer = {k: 0.0 for k in ("check", "db", "table", "device_setup", "parse_wait", "device_wait", "gpu_h2d", "gpu_counts",
-                              "gpu_presence", "gpu_abund", "gpu_explain", "d2h", "assemble", "writes", "cohort_files", "dense_fallback_blocks", "total")}
+                              "gpu_presence", "gpu_abund", "gpu_explain", "gpu_gather", "d2h", "assemble", "writes", "cohort_files", "dense_fallback_blocks", "total")}
     t_all = time.perf_counter()
     t0 = time.perf_counter()
     plan = check_inputs(args, files)
@@ -401,8 +476,21 @@ def main(args, files: List[str]) -> dict:
     # YACHT_COHORT_EXPLAIN=host: every sample's residual by its own host-form yh_explain call, as before the batched pass
     # (A/B checks); otherwise only the samples whose tables the host recomputed below take it
     device_explain = want_residual and os.environ.get("YACHT_COHORT_EXPLAIN") != "host"
+    gather_plan = None
+    if getattr(args, "gather", False):
+        from . import gather
+
+        gather_plan = gather.gather_options(args, len(paths))  # (coverages, min_hits)
+        gather_top = gather.gather_top(args, len(paths))
+        gather_idx = [[float(c) for c in user_covs].index(c) for c in gather_plan[0]]  # which user coverages are ranked
+        gather_frames = []  # (stem, the sample's gather_profile.tsv frame), in cohort order
+    # YACHT_COHORT_GATHER=loop: every sample's ranking by its own host-form yh_gather calls (A/B checks); otherwise only
+    # the samples whose tables the host recomputed below take them
+    device_gather = gather_plan is not None and os.environ.get("YACHT_COHORT_GATHER") != "loop"
     dev = _Device(db, covs, ksize, ani_thresh, t_thr, abund_samples=min(BLOCK, len(paths)) if want_abundance else 0,
-                  residual_sets=len(user_covs) if device_explain else 0)
+                  residual_sets=len(user_covs) if device_explain else 0,
+                  **(dict(gather_sets=gather_idx, gather_min_hits=gather_plan[1], gather_top=gather_top, n_user=len(user_covs),
+                          max_samples=len(paths)) if device_gather else {}))
     timer["device_setup"] = time.perf_counter() - t0
 
     blocks = [list(range(i, min(i + BLOCK, len(paths)))) for i in range(0, len(paths), BLOCK)]
@@ -414,15 +502,17 @@ def main(args, files: List[str]) -> dict:
     parse_pool = ThreadPoolExecutor(max(1, int(args.num_threads)))
 
     def parse(block):
-        if want_residual:
+        if want_residual or gather_plan is not None:
             return [parse_pool.submit(_load_for_residual, paths[i], ksize, want_abundance) for i in block]
         return [parse_pool.submit(_load_mins_abund if want_abundance else _load_mins, paths[i], ksize) for i in block]
 
     def assemble(block, mins, got, abunds=None, sigs=None):
         rows, pv, pres, ncov = got[:4]
         t0 = time.perf_counter()
+        if device_gather:  # the block's rows [gather coverages][samples][longest ranking] and their counts
+            g_rows, g_n = got[-1]
         if device_explain:  # the block's flags [passes][hashes] and totals [passes][samples][8][2]
-            x_flags, x_totals = got[-1]
+            x_flags, x_totals = got[-2 if device_gather else -1]
             x_offs = np.zeros(len(block) + 1, dtype=np.int64)
             x_offs[1:] = np.cumsum([m.size for m in mins])
         smp = rows[:, 0]
@@ -470,9 +560,20 @@ def main(args, files: List[str]) -> dict:
                 total = int(abunds[s].sum(dtype=np.uint64))
                 frames = [abundance.append_columns(f, *depth, total) for f in frames]
             frames = ry.trim_results(frames)
-            explained = None
-            if want_residual:
+            explained = ranked = None
+            if want_residual or gather_plan is not None:
                 call_sets = [refs[df["in_sample_est"].to_numpy().astype(bool)] for df in (frames if has_raw else frames[1:])]
+            if gather_plan is not None:
+                if device_gather and not recomputed:  # the device's present bytes ARE these call sets: the block's ranking
+                    ranks = [g_rows[g, s, :int(g_n[g, s])] for g in range(len(gather_idx))]
+                else:  # the host's own tables: one host-form call per gather coverage
+                    t1 = time.perf_counter()
+                    ranks = gather.gather_call_sets(db, mins[s], abunds[s] if abunds is not None else None,
+                                                    [call_sets[u] for u in gather_idx], gather_plan[1], gather_top)
+                    timer["gpu_gather"] += time.perf_counter() - t1
+                ranked = gather.sample_frame(sigs[s], gather_plan[0], ranks, names)
+                gather_frames.append((stem, ranked))
+            if want_residual:
                 if device_explain and not recomputed:  # the device's present bytes ARE these call sets: the block's pass answered them
                     flags = [x_flags[c // MAX_SETS, x_offs[s]:x_offs[s + 1]] for c in range(len(call_sets))]
                     totals = [x_totals[c // MAX_SETS, s] for c in range(len(call_sets))]
@@ -497,7 +598,7 @@ def main(args, files: List[str]) -> dict:
                         part[c] = hit[c].to_numpy()
                     presence.append(pd.DataFrame(part, columns=presence_columns))
             futures.append(pool.submit(_write_one, os.path.join(results_folder, stem), frames, covs, has_raw, args.keep_raw,
-                                       args.show_all, want_abundance, explained))
+                                       args.show_all, want_abundance, explained, ranked))
         timer["assemble"] += time.perf_counter() - t0
 
     try:
@@ -508,13 +609,13 @@ def main(args, files: List[str]) -> dict:
             t0 = time.perf_counter()
             mins = [f.result() for f in parsing]
             abunds = sigs = None
-            if want_residual:  # (abundances where the sketch tracks them; --abundance has checked that every one does)
+            if want_residual or gather_plan is not None:  # (abundances where the sketch tracks them; --abundance has checked that every one does)
                 mins, abunds, sigs = [x[0] for x in mins], [x[1] for x in mins], [x[2] for x in mins]
             elif want_abundance:
                 mins, abunds = [x[0] for x in mins], [x[1] for x in mins]
             timer["parse_wait"] += time.perf_counter() - t0
             parsing = parse(blocks[j + 1]) if j + 1 < len(blocks) else []
-            b = dev.launch(mins, abunds if want_abundance else None, abunds if device_explain and not want_abundance else None)
+            b = dev.launch(mins, abunds if want_abundance else None, abunds if (device_explain or device_gather) and not want_abundance else None)
             if pending is not None:
                 assemble(*pending)  # (block j - 1 on the host while block j is on the device and block j + 1 is parsed)
             pending = (block, mins, dev.collect(b, timer), abunds, sigs)
@@ -532,6 +633,9 @@ def main(args, files: List[str]) -> dict:
     pd.DataFrame(summary, columns=SAMPLE_COLUMNS + (residual.COHORT_COLUMNS if want_residual else [])).to_csv(os.path.join(results_folder, "cohort_samples.tsv"), sep="\t", index=False)
     (pd.concat(presence, ignore_index=True) if presence else pd.DataFrame(columns=presence_columns)).to_csv(
         os.path.join(results_folder, "cohort_presence.tsv"), sep="\t", index=False)
+    if gather_plan is not None:
+        gather.cohort_frame([g[0] for g in gather_frames], [g[1] for g in gather_frames]).to_csv(
+            os.path.join(results_folder, gather.COHORT_GATHER_NAME), sep="\t", index=False)
     timer["cohort_files"] = time.perf_counter() - t0
     timer["total"] = time.perf_counter() - t_all
     logger.info(f"Saved results of {len(paths)} samples to {results_folder}.")

@@ -1467,6 +1467,100 @@ int yh_explain_batch(yh_db* db, const uint64_t* samples, const uint64_t* sample_
     return rc;
 }
 
+// ---- the ranking for a block of samples, each with its own candidates (yh_gather.hip) ---------------------------------
+static bool gather_batch_args_ok(uint32_t n_samples, uint8_t cand_mask, uint32_t min_hits, uint64_t cap_rows, uint64_t total_hashes) {
+    if (!explain_batch_samples_ok(n_samples)) return false;
+    if (min_hits == 0) { yh_set_error("min_hits must be at least 1"); return false; }
+    if (cand_mask == 0) { yh_set_error("cand_mask must name at least one bit of the member bytes"); return false; }
+    if (cap_rows > YH_GATHER_BATCH_MAX_ROWS) { yh_set_error("cap_rows must be at most %d: the rounds are enqueued without a host sync", YH_GATHER_BATCH_MAX_ROWS); return false; }
+    if (total_hashes >> 32) { yh_set_error("yh_gather_batch takes blocks below 2^32 hashes"); return false; }
+    return true;
+}
+
+int yh_gather_batch_device(yh_db* db, const uint64_t* d_samples, const uint64_t* d_sample_offsets, const uint32_t* d_abund,
+                           uint32_t n_samples, uint64_t total_hashes, const uint8_t* d_members, uint8_t cand_mask, uint32_t min_hits,
+                           yh_gather_row* d_rows, uint64_t cap_rows, uint32_t* d_owner, uint32_t* d_n_rows, uint8_t* d_more) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (!gather_batch_args_ok(n_samples, cand_mask, min_hits, cap_rows, total_hashes)) return YH_ERR_INVALID_ARG;
+    if (!d_n_rows || !d_more || !d_sample_offsets || (total_hashes && !d_samples) || (total_hashes && db->n_refs && !d_members) ||
+        (cap_rows && !d_rows)) {
+        yh_set_error("null device pointer");
+        return YH_ERR_INVALID_ARG;
+    }
+    YH_TRY(explain_supported(db));
+    YH_TRY(db_select(db));
+    YH_TRY(pipe_join(db));  // (no step context, batch slot or work list is read or written: nothing else to note)
+    fin_join(db);           // (member rows made from rows the rows pack / unpack wrote on the finish stream)
+    return yh_q_gather_batch(db, (const u64*)d_samples, (const u64*)d_sample_offsets, d_abund, n_samples, total_hashes, d_members,
+                             cand_mask, min_hits, d_rows, cap_rows, d_owner, d_n_rows, d_more);
+}
+
+int yh_gather_batch(yh_db* db, const uint64_t* samples, const uint64_t* sample_offsets, const uint32_t* abund, uint32_t n_samples,
+                    const uint8_t* members, uint8_t cand_mask, uint32_t min_hits, yh_gather_row* rows, uint64_t cap_rows,
+                    uint32_t* owner, uint32_t* n_rows, uint8_t* more) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (!sample_offsets || !n_rows || !more) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+    if (!explain_batch_samples_ok(n_samples)) return YH_ERR_INVALID_ARG;
+    const u64 total = sample_offsets[n_samples];
+    if (!gather_batch_args_ok(n_samples, cand_mask, min_hits, cap_rows, total)) return YH_ERR_INVALID_ARG;
+    const u64 N = db->n_refs;
+    const u64 BN = (u64)n_samples * N;
+    if (sample_offsets[0] != 0 || (total && !samples) || (N && !members) || (cap_rows && !rows)) {
+        yh_set_error("bad sample arrays, null member table or null rows");
+        return YH_ERR_INVALID_ARG;
+    }
+    for (uint32_t s = 0; s < n_samples; ++s) {
+        if (sample_offsets[s + 1] < sample_offsets[s] ||
+            yh_q_check_sorted_host((const u64*)samples + sample_offsets[s], sample_offsets[s + 1] - sample_offsets[s]) != YH_OK) {
+            yh_set_error("sample %u is not strictly ascending", s);
+            return YH_ERR_UNSORTED;
+        }
+    }
+    YH_TRY(explain_supported(db));
+    YH_TRY(db_select(db));
+    u64 *d_s = nullptr, *d_o = nullptr;
+    u32 *d_a = nullptr, *d_owner = nullptr;
+    u8* d_bytes = nullptr;  // the rows, the row counts, the `more` bytes, the member rows
+    const u64 row_bytes = (u64)n_samples * cap_rows * sizeof(yh_gather_row);
+    const u64 off_n = (row_bytes + 15) & ~15ull, off_more = off_n + (u64)n_samples * sizeof(u32), off_members = (off_more + n_samples + 15) & ~15ull;
+    int rc = YH_OK;
+    do {
+        if (yh_tmalloc(db, (void**)&d_s, std::max<u64>(total, 2) * sizeof(u64)) != hipSuccess ||
+            yh_tmalloc(db, (void**)&d_o, (u64)(n_samples + 1) * sizeof(u64)) != hipSuccess ||
+            (abund && yh_tmalloc(db, (void**)&d_a, std::max<u64>(total, 4) * sizeof(u32)) != hipSuccess) ||
+            (owner && yh_tmalloc(db, (void**)&d_owner, std::max<u64>(total, 4) * sizeof(u32)) != hipSuccess) ||
+            yh_tmalloc(db, (void**)&d_bytes, off_members + std::max<u64>(BN, 16)) != hipSuccess) { yh_set_error("device allocation failed"); rc = YH_ERR_OOM; break; }
+        if ((total && hipMemcpyAsync(d_s, samples, total * sizeof(u64), hipMemcpyHostToDevice, db->stream) != hipSuccess) ||
+            hipMemcpyAsync(d_o, sample_offsets, (u64)(n_samples + 1) * sizeof(u64), hipMemcpyHostToDevice, db->stream) != hipSuccess ||
+            (abund && total && hipMemcpyAsync(d_a, abund, total * sizeof(u32), hipMemcpyHostToDevice, db->stream) != hipSuccess) ||
+            (BN && hipMemcpyAsync(d_bytes + off_members, members, BN, hipMemcpyHostToDevice, db->stream) != hipSuccess)) {
+            yh_set_error("gather upload failed"); rc = YH_ERR_HIP; break;
+        }
+        if ((rc = yh_gather_batch_device(db, (const uint64_t*)d_s, (const uint64_t*)d_o, abund ? d_a : nullptr, n_samples, total,
+                                         d_bytes + off_members, cand_mask, min_hits, (yh_gather_row*)d_bytes, cap_rows, d_owner,
+                                         (uint32_t*)(d_bytes + off_n), d_bytes + off_more)) != YH_OK) break;
+        // the counts first: only the rows a sample has are copied (rows behind n_rows[s] are not written on the host either)
+        if (hipMemcpyAsync(n_rows, d_bytes + off_n, (u64)n_samples * sizeof(u32), hipMemcpyDeviceToHost, db->stream) != hipSuccess ||
+            hipMemcpyAsync(more, d_bytes + off_more, n_samples, hipMemcpyDeviceToHost, db->stream) != hipSuccess ||
+            hipStreamSynchronize(db->stream) != hipSuccess) {
+            yh_set_error("gather download failed: %s", hipGetErrorString(hipGetLastError()));
+            rc = YH_ERR_HIP;
+            break;
+        }
+        bool down_ok = !owner || !total || hipMemcpyAsync(owner, d_owner, total * sizeof(u32), hipMemcpyDeviceToHost, db->stream) == hipSuccess;
+        for (uint32_t s = 0; s < n_samples && down_ok; ++s)
+            if (n_rows[s])
+                down_ok = hipMemcpyAsync(rows + (u64)s * cap_rows, d_bytes + (u64)s * cap_rows * sizeof(yh_gather_row),
+                                         (u64)n_rows[s] * sizeof(yh_gather_row), hipMemcpyDeviceToHost, db->stream) == hipSuccess;
+        if (!down_ok || hipStreamSynchronize(db->stream) != hipSuccess) {
+            yh_set_error("gather download failed: %s", hipGetErrorString(hipGetLastError()));
+            rc = YH_ERR_HIP;
+        }
+    } while (0);
+    yh_tfree(db, d_s); yh_tfree(db, d_o); yh_tfree(db, d_a); yh_tfree(db, d_owner); yh_tfree(db, d_bytes);
+    return rc;
+}
+
 // ---- sharded run: the step in two halves around the exchange of the subset bits -----------------------
 int yh_db_set_ghosts(yh_db* db, uint64_t ghost_begin, uint64_t n_ghost, const uint32_t* d_ghost_src) {
     if (!db_ok(db)) return YH_ERR_INVALID_ARG;

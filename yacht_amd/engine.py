@@ -132,6 +132,18 @@ def check_gather_limits(min_hits, cap_rows, n_refs: int) -> Tuple[int, int]:
     return int(min_hits), min(int(cap_rows), int(n_refs))
 
 
+def check_gather_batch_limits(cand_mask, min_hits, cap_rows, n_refs: int) -> Tuple[int, int, int]:
+    """(cand_mask, min_hits, cap_rows) of RefDB.gather_batch as integers, or ValueError: cand_mask in [1, 255], min_hits in
+    [1, 2**32 - 1], cap_rows None (min(n_refs, YH_GATHER_BATCH_MAX_ROWS)) or in [0, YH_GATHER_BATCH_MAX_ROWS]: the rounds of a
+    block are enqueued without a host sync, so the cap bounds them.  Host only: no library call."""
+    if int(cand_mask) != cand_mask or not 1 <= int(cand_mask) <= 0xFF:
+        raise ValueError(f"cand_mask must be an integer in [1, 255], not {cand_mask}")
+    if cap_rows is not None and (int(cap_rows) != cap_rows or not 0 <= int(cap_rows) <= _lib.YH_GATHER_BATCH_MAX_ROWS):
+        raise ValueError(f"cap_rows must be None or an integer in [0, {_lib.YH_GATHER_BATCH_MAX_ROWS}], not {cap_rows}")
+    min_hits, cap = check_gather_limits(min_hits, cap_rows, n_refs)
+    return int(cand_mask), min_hits, min(cap, _lib.YH_GATHER_BATCH_MAX_ROWS)
+
+
 def check_members(members, n_samples: int, n_refs: int) -> np.ndarray:
     """The member rows of RefDB.explain_batch as uint8 [n_samples, n_refs], or ValueError: 1..256 samples, one row per
     sample, one byte per reference, each in [0, 127].  Host only: no library call."""
@@ -391,6 +403,55 @@ class RefDB:
                                               int(min_hits), C.c_void_p(d_rows), int(cap_rows), C.c_void_p(d_owner),
                                               C.byref(n_rows), C.byref(more)))
         return int(n_rows.value), bool(more.value)
+
+    def gather_batch(self, samples: Sequence[np.ndarray], members, cand_mask: int = 1, abunds=None, min_hits: int = 1,
+                     cap_rows: Optional[int] = None, want_owner: bool = False):
+        """gather for a block of 1..256 samples in the same launches (yh_gather_batch).  members: uint8 [len(samples),
+        n_refs]; reference j is a candidate of sample s when members[s, j] & cand_mask is non-zero (the member rows of
+        explain_batch, one bit per call set).  abunds: as for explain_batch.  cap_rows: at most this many rows per sample,
+        None = min(n_refs, YH_GATHER_BATCH_MAX_ROWS), never above that maximum.  Returns (rows, more, owners): a list of
+        GATHER_ROW_DTYPE arrays, a list of booleans and a list of uint32 owner arrays (None without want_owner), each equal
+        to gather's for that sample alone."""
+        b = len(samples)
+        if not 1 <= b <= _lib.YH_BATCH_MAX_SAMPLES:
+            raise ValueError(f"a block holds 1..{_lib.YH_BATCH_MAX_SAMPLES} samples, not {b}")
+        members = np.asarray(members)
+        if members.ndim != 2 or members.shape != (b, self.n_refs):
+            raise ValueError(f"members must be [n_samples, n_refs] = [{b}, {self.n_refs}], not {list(members.shape)}")
+        if members.size and members.dtype.kind not in "iub":
+            raise ValueError(f"member bytes must be integers, not {members.dtype}")
+        members = np.ascontiguousarray(members, dtype=np.uint8)
+        cand_mask, min_hits, cap = check_gather_batch_limits(cand_mask, min_hits, cap_rows, self.n_refs)
+        samples = [_as_u64(s) for s in samples]
+        cat_ab = None
+        if abunds is not None:
+            if len(abunds) != b:
+                raise ValueError(f"{len(abunds)} abundance arrays for {b} samples")
+            if any(a is not None for a in abunds):
+                parts = [np.ones(s.size, dtype=np.uint32) if a is None else check_abundances(s, a)[1] for s, a in zip(samples, abunds)]
+                cat_ab = np.ascontiguousarray(np.concatenate(parts), dtype=np.uint32)
+        values, offsets = pack_csr(samples)
+        rows = np.zeros((b, max(cap, 1)), dtype=GATHER_ROW_DTYPE)
+        owner = np.full(values.size, _lib.YH_GATHER_NOBODY, dtype=np.uint32) if want_owner else None
+        n_rows, more = np.zeros(b, dtype=np.uint32), np.zeros(b, dtype=np.uint8)
+        _lib.check(self._lib.yh_gather_batch(self._h, _ptr(values), _ptr(offsets), _ptr(cat_ab), b, _ptr(members), cand_mask, min_hits,
+                                             _ptr(rows), cap, _ptr(owner), _ptr(n_rows), _ptr(more)))
+        return ([rows[s, :int(n_rows[s])].copy() for s in range(b)], [bool(m) for m in more],
+                [owner[int(offsets[s]):int(offsets[s + 1])] for s in range(b)] if want_owner else None)
+
+    def gather_batch_device(self, d_samples: int, d_offsets: int, d_abund: int, n_samples: int, total_hashes: int, d_members: int,
+                            cand_mask: int, min_hits: int, d_rows: int, cap_rows: int, d_owner: int, d_n_rows: int, d_more: int) -> None:
+        """yh_gather_batch_device: the block as for explain_batch_device, uint32 abundances (0: all 1) and uint8 [n_samples][N]
+        member rows in; [n_samples][cap_rows] rows of GATHER_ROW_DTYPE, uint32 [total_hashes] owners (0: none), uint32
+        [n_samples] row counts and uint8 [n_samples] `more` bytes out, all on the device.  Does not synchronize the host."""
+        if not 1 <= int(cand_mask) <= 0xFF:
+            raise ValueError(f"cand_mask must be an integer in [1, 255], not {cand_mask}")
+        if not 0 <= int(min_hits) <= 0xFFFFFFFF or int(cap_rows) < 0:
+            raise ValueError(f"min_hits must lie in [0, 2**32 - 1] and cap_rows be >= 0, not {min_hits} and {cap_rows}")
+        _lib.check(self._lib.yh_gather_batch_device(self._h, C.c_void_p(d_samples), C.c_void_p(d_offsets), C.c_void_p(d_abund),
+                                                    n_samples, total_hashes, C.c_void_p(d_members), int(cand_mask), int(min_hits),
+                                                    C.c_void_p(d_rows), int(cap_rows), C.c_void_p(d_owner), C.c_void_p(d_n_rows),
+                                                    C.c_void_p(d_more)))
 
     def explain_batch(self, samples: Sequence[np.ndarray], members, abunds=None, want_flags: bool = True):
         """explain for a block of 1..256 samples, each with its own member row, in one lookup launch (yh_explain_batch).

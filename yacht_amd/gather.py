@@ -8,10 +8,12 @@ with exactly those.  Everything here is numpy / pandas on its rows: no device, n
 from __future__ import annotations
 
 import os
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 import numpy as np
 import pandas as pd
+
+from . import _lib
 
 GATHER_COLUMNS = [
     "min_coverage",
@@ -26,26 +28,32 @@ GATHER_COLUMNS = [
     "f_unique_weighted",
 ]
 GATHER_NAME = "gather_profile.tsv"
+COHORT_GATHER_NAME = "cohort_gather.tsv"
+TOP_MAX_COHORT = _lib.YH_GATHER_BATCH_MAX_ROWS  # a block's rounds are enqueued without a host sync: the cap bounds them
 MSG_OPTION_WITHOUT_GATHER = "{0} needs --gather."
 MSG_COVERAGE_NOT_LISTED = "--gather_coverage {0} is not one of the --min_coverage_list values {1}."
 MSG_BAD_MIN_HITS = "--gather_min_hits must be at least 1, not {0}."
-MSG_COHORT = ("--gather takes one sample file, not {0}: the ranking of a cohort's samples is not built yet. "
-              "Run the samples one at a time, or drop --gather.")
+MSG_BAD_TOP = "--gather_top must be at least 1, not {0}."
+MSG_TOP_ABOVE_MAX = "--gather_top must be at most {1} for a cohort, not {0}: a block's rounds are queued on the device up to that bound."
+MSG_COHORT = ("--gather takes one sample file, not {0}: a cohort's samples are ranked a block at a time on the device, which "
+              "needs a bound on the rows.  Add --gather_top K (at most %d), run the samples one at a time, or drop --gather." % TOP_MAX_COHORT)
 
 
 def gather_options(args, n_files: int = 1):
     """(coverages, min_hits) of a `yacht run --gather`, or None without the flag.  coverages: the --min_coverage_list values
     the ranking is made for, descending -- all of them, or the --gather_coverage ones.  ValueError when an option comes
-    without --gather, names a coverage outside the list, asks for min_hits below 1, or when there is more than one sample
-    file.  Host only: it runs before anything is written or any device work."""
+    without --gather, names a coverage outside the list, asks for min_hits below 1, when --gather_top is refused (gather_top),
+    or when there is more than one sample file and no --gather_top.  Host only: it runs before anything is written or any
+    device work."""
     want = bool(getattr(args, "gather", False))
     covs = getattr(args, "gather_coverage", None)
     min_hits = getattr(args, "gather_min_hits", None)
     if not want:
         if covs is not None:
             raise ValueError(MSG_OPTION_WITHOUT_GATHER.format("--gather_coverage"))
+        gather_top(args, n_files)
         return None
-    if n_files > 1:
+    if gather_top(args, n_files) is None and n_files > 1:
         raise ValueError(MSG_COHORT.format(n_files))
     min_hits = 1 if min_hits is None else int(min_hits)
     if min_hits < 1:
@@ -60,6 +68,21 @@ def gather_options(args, n_files: int = 1):
     return sorted(set(covs), reverse=True), min_hits
 
 
+def gather_top(args, n_files: int = 1) -> Optional[int]:
+    """K of `--gather_top K`: at most K organisms are ranked per sample and coverage (cap_rows of the ranking); None without
+    the option.  ValueError when it comes without --gather, is below 1, or -- for a cohort -- above TOP_MAX_COHORT."""
+    top = getattr(args, "gather_top", None)
+    if top is None:
+        return None
+    if not bool(getattr(args, "gather", False)):
+        raise ValueError(MSG_OPTION_WITHOUT_GATHER.format("--gather_top"))
+    if int(top) < 1:
+        raise ValueError(MSG_BAD_TOP.format(top))
+    if n_files > 1 and int(top) > TOP_MAX_COHORT:
+        raise ValueError(MSG_TOP_ABOVE_MAX.format(top, TOP_MAX_COHORT))
+    return int(top)
+
+
 def candidate_table(n_refs: int, call_set) -> np.ndarray:
     """The candidate table of RefDB.gather, uint8 [n_refs]: 1 at the manifest rows of one call set."""
     rows = np.asarray(call_set, dtype=np.int64)
@@ -70,9 +93,9 @@ def candidate_table(n_refs: int, call_set) -> np.ndarray:
     return table
 
 
-def gather_call_sets(db, sample, abund, call_sets: Sequence, min_hits: int = 1) -> List[np.ndarray]:
-    """One RefDB.gather call per call set (arrays of manifest row indices): the rows of each, uncapped."""
-    return [db.gather(sample, candidate_table(db.n_refs, s), abund, min_hits=min_hits)[0] for s in call_sets]
+def gather_call_sets(db, sample, abund, call_sets: Sequence, min_hits: int = 1, cap_rows: Optional[int] = None) -> List[np.ndarray]:
+    """One RefDB.gather call per call set (arrays of manifest row indices): the rows of each, at most cap_rows (None: uncapped)."""
+    return [db.gather(sample, candidate_table(db.n_refs, s), abund, min_hits=min_hits, cap_rows=cap_rows)[0] for s in call_sets]
 
 
 def gather_frame(covs: Sequence[float], rows: Sequence, names, n_hashes: int, abund_total: int) -> pd.DataFrame:
@@ -94,11 +117,32 @@ def gather_frame(covs: Sequence[float], rows: Sequence, names, n_hashes: int, ab
     return frame.astype({"rank": np.int64, "num_overlap": np.int64, "num_unique": np.int64}) if len(frame) else frame
 
 
-def write_profile(results_folder: str, sample_sig, covs: Sequence[float], rows: Sequence, names) -> pd.DataFrame:
-    """results/gather_profile.tsv from the rows of every chosen coverage.  Returns the frame."""
+def sample_frame(sample_sig, covs: Sequence[float], rows: Sequence, names) -> pd.DataFrame:
+    """gather_frame for a sample's signature: the fractions are over its hashes and the sum of its abundances."""
     mh = sample_sig.minhash
     n_hashes = len(mh)
     abund_total = n_hashes if mh.abundances is None else int(np.asarray(mh.abundances, dtype=np.uint64).sum(dtype=np.uint64))
-    frame = gather_frame(covs, rows, names, n_hashes, abund_total)
+    return gather_frame(covs, rows, names, n_hashes, abund_total)
+
+
+def write_frame(results_folder: str, frame: pd.DataFrame) -> None:
     frame.to_csv(os.path.join(results_folder, GATHER_NAME), sep="\t", index=False)
+
+
+def write_profile(results_folder: str, sample_sig, covs: Sequence[float], rows: Sequence, names) -> pd.DataFrame:
+    """results/gather_profile.tsv from the rows of every chosen coverage.  Returns the frame."""
+    frame = sample_frame(sample_sig, covs, rows, names)
+    write_frame(results_folder, frame)
     return frame
+
+
+def cohort_frame(stems: Sequence[str], frames: Sequence[pd.DataFrame]) -> pd.DataFrame:
+    """results/cohort_gather.tsv: the samples' gather_profile.tsv frames in long form, one after the other in the order
+    given, behind a `sample` column.  No sample (or only empty frames): the columns alone."""
+    parts = []
+    for stem, frame in zip(stems, frames):
+        if len(frame):
+            part = frame.copy()
+            part.insert(0, "sample", stem)
+            parts.append(part)
+    return pd.concat(parts, ignore_index=True) if parts else pd.DataFrame(columns=["sample"] + GATHER_COLUMNS)

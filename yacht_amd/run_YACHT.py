@@ -20,6 +20,7 @@ from pathlib import Path
 
 import pandas as pd
 
+from . import _lib
 from . import hypothesis_recovery_src as hr
 from . import phases
 from . import utils
@@ -62,11 +63,15 @@ ARGUMENTS = (
     ("--gather", dict(action="store_true",
                       help="Also rank the organisms called present by the sample hashes each adds, a minimum set cover as "
                            "`sourmash gather` makes it: results/gather_profile.tsv (per min_coverage and rank: the organism, the "
-                           "sample hashes it holds, those no higher-ranked organism took, and their abundance).  One sample file.")),
+                           "sample hashes it holds, those no higher-ranked organism took, and their abundance).  One sample file; "
+                           "a cohort with --gather_top: results/<stem>/gather_profile.tsv per sample and results/cohort_gather.tsv.")),
     ("--gather_min_hits", dict(type=int, default=1,
                                help="Stop the ranking when the best remaining organism adds fewer sample hashes than this (with --gather).")),
     ("--gather_coverage", dict(type=float, nargs="+", default=None,
                                help="The --min_coverage_list values the ranking is made for (with --gather; default: all of them).")),
+    ("--gather_top", dict(type=int, default=None,
+                          help="Rank at most this many organisms per sample and coverage (with --gather; default: no bound).  "
+                               "A cohort needs it, at most %d: its samples are ranked a block at a time on the device." % _lib.YH_GATHER_BATCH_MAX_ROWS)),
 )
 
 # messages the reference raises with (callers and its tests match on them)
@@ -156,10 +161,11 @@ def main(args) -> None:
 
         residual_cov = residual.residual_coverage(args)  # (ValueError before anything is written or any device work)
     gather_plan = None
-    if getattr(args, "gather", False) or getattr(args, "gather_coverage", None) is not None:
+    if getattr(args, "gather", False) or getattr(args, "gather_coverage", None) is not None or getattr(args, "gather_top", None) is not None:
         from . import gather
 
         gather_plan = gather.gather_options(args, len(files))  # (ValueError before anything is written or any device work)
+        gather_cap = gather.gather_top(args, len(files))
     if len(files) > 1:
         from . import cohort
 
@@ -233,7 +239,7 @@ def main(args) -> None:
             all_sets = _residual.call_sets_of(manifest["organism_name"], results if has_raw else results[1:])
             gather_sets = [all_sets[all_covs.index(c)] for c in gather_plan[0]]
             gather_rows = gather.gather_call_sets(hr._LAST_RUN["db"], hr._LAST_RUN["mins"],
-                                                  _residual.sample_abundances_or_none(sample_sig), gather_sets, gather_plan[1])
+                                                  _residual.sample_abundances_or_none(sample_sig), gather_sets, gather_plan[1], gather_cap)
     hr.release_reference_dbs()
     results = trim_results(results)
 
