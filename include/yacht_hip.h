@@ -301,6 +301,7 @@ int yh_run_device_join(yh_db* db);
  *     yh_explain_members_rows_device                         |                                       |
  *   yh_gather / yh_gather_device                             | yes (no step state is read or written) | yes
  *   yh_gather_batch / yh_gather_batch_device                 | yes (no step state is read or written) | yes
+ *   yh_lca / yh_lca_device, yh_db_set_taxonomy               | yes (no step state is read or written) | yes
  *   yh_db_set_stream                                         | yes (drains the old stream first)      | yes
  *   (*) the CURRENT context = the one named by the last yh_run_local*_device / yh_run_finish*_device call (0 at start).
  * Every query entry point first completes the pending stages of pipelined steps (yh_run_device_join) by itself.          */
@@ -626,6 +627,44 @@ int yh_gather_batch_device(yh_db* db, const uint64_t* d_samples, const uint64_t*
 int yh_gather_batch(yh_db* db, const uint64_t* samples, const uint64_t* sample_offsets, const uint32_t* abund, uint32_t n_samples,
                     const uint8_t* members, uint8_t cand_mask, uint32_t min_hits, yh_gather_row* rows, uint64_t cap_rows,
                     uint32_t* owner, uint32_t* n_rows, uint8_t* more);
+
+/* ---- every sample hash classified by the LOWEST COMMON ANCESTOR of its holders (additive in ABI 8) ---------------------------
+ * yh_run, yh_abund, yh_explain and yh_gather answer per reference or per call set; a sample hash held by three strains of one
+ * species is evidence for that species and for none of the strains.  With a taxonomy over the references this answers, for
+ * every sample hash, the deepest node all of its holders sit under, and per node how many hashes resolve exactly there.
+ * The taxonomy is a rooted tree of n_nodes nodes: node 0 is the root, parent[0] = 0 and depth[0] = 0; for v > 0, parent[v] < v
+ * and depth[v] = depth[parent[v]] + 1 <= YH_LCA_MAX_DEPTH; leaf[j] < n_nodes is the node of reference j, which may be an
+ * internal node, or the root for a reference without a lineage.
+ * yh_db_set_taxonomy is host-form and synchronous: it validates all of the above (YH_ERR_INVALID_ARG on a violation, and an
+ * earlier taxonomy stays in place), completes pending pipelined stages, uploads the three arrays and runs one kernel over the
+ * shared-hash index that writes lca_shared[gi] = the LCA of leaf[holder] over the posting list of shared hash gi (a handle
+ * without shared hashes launches nothing).  A second call replaces the first; n_nodes == 0 removes the taxonomy.  The arrays
+ * (5 bytes per node, 4 per reference and per shared hash) come from the handle's buffer cache and are freed with the handle;
+ * yh_db_get_taxonomy reports n_nodes (0: none set) and their bytes.  yh_db_info is unchanged.
+ * yh_lca_device: for every sample hash h of S (strictly ascending)
+ *   node[h] = YH_LCA_NONE       when no reference of the database holds h
+ *   node[h] = leaf[j]           when j is its only holder
+ *   node[h] = lca_shared[gi]    when it is shared hash gi
+ * and for every node v
+ *   counts[v][0] = #{h in S : node[h] == v},   counts[v][1] = sum of abund(h) over the same hashes (NULL: every abund(h) = 1).
+ * These are DIRECT assignments: the clade sums (a node plus everything under it) are one reverse sweep on the host.  d_counts
+ * is cleared by the call.  d_node may be NULL: the counts only.  n_sample == 0 or an empty database: zero counts, and no node
+ * is written.  All outputs are integers and do not depend on arrival order.  Like yh_explain_device the pass reads no step
+ * context, batch slot or work list (interleaving table above: yes / yes), completes pending pipelined stages first, is
+ * enqueued on the handle's stream and does not sync the host.  yh_lca is the synchronous host form: it validates the sample's
+ * ordering (YH_ERR_UNSORTED), uploads, runs and downloads.
+ * YH_ERR_UNSUPPORTED: no taxonomy set; a handle without the directory or the index (YH_DB_NO_DIRECTORY, YH_DB_NO_INDEX,
+ * YH_DB_PAIRWISE_ONLY: yh_db_set_taxonomy refuses those too); ghosts registered (yh_db_set_ghosts).
+ * Hash-range shards: each hash lives on one rank, so over the ranks the nodes concatenate and the counts ADD.  Nothing is
+ * built for shards.
+ * (No reference counterpart: its route to taxonomy is `yacht convert`.  Nearest elsewhere: `sourmash lca summarize`.)          */
+#define YH_LCA_MAX_DEPTH 16
+#define YH_LCA_NONE 0xffffffffu
+int yh_db_set_taxonomy(yh_db* db, const uint32_t* parent, const uint8_t* depth, uint32_t n_nodes, const uint32_t* leaf /* [N] */);
+int yh_db_get_taxonomy(yh_db* db, uint32_t* n_nodes, uint64_t* device_bytes);
+int yh_lca_device(yh_db* db, const uint64_t* d_sample, const uint32_t* d_abund /* NULL: all 1 */, uint64_t n_sample,
+                  uint32_t* d_node /* [n_sample] or NULL */, uint64_t* d_counts /* [n_nodes][2] */);
+int yh_lca(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_t n_sample, uint32_t* node, uint64_t* counts);
 
 /* ---- the subset words of a block in compact form (ABI 5) ----------------------------------------------------------------
  * Between the two halves of a batched hash-range run every rank needs the OR of all ranks' subset words.  The dense row

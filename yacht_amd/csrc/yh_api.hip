@@ -3,6 +3,7 @@
 #include "yh_abund.h"
 #include "yh_explain.h"
 #include "yh_gather.h"
+#include "yh_lca.h"
 #include "yh_sort.h"
 #include "yh_pack.h"
 
@@ -648,6 +649,7 @@ int yh_db_destroy(yh_db* db) {
             yh_dfree(db, db->ctx_count[c]);
         }
     }
+    yh_dfree(db, yh_lca_taxonomy_swap(db, nullptr));  // (the taxonomy lives beside the handle: yh_lca.h)
     void* ptrs[] = {db->d_values, db->d_offsets, db->d_sizes, db->d_g, db->d_po, db->d_pr, db->d_pg, db->d_nshared,
                     db->d_dh, db->d_dref, db->d_dir, db->d_bkt, db->d_cbkt, db->d_ovf_keys, db->d_ovf_vals,
                     db->d_rpo, db->d_rg, db->d_rrec, db->d_rrecx, db->d_filter, db->d_hrec, db->d_hrecx, db->d_hmult, db->d_hpo,
@@ -1319,6 +1321,142 @@ int yh_explain(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_
         }
     } while (0);
     yh_tfree(db, d_a); yh_tfree(db, d_bytes);
+    return rc;
+}
+
+// ---- every sample hash classified by the lowest common ancestor of its holders (yh_lca.hip) ---------------------
+static int lca_handle_supported(yh_db* db, const char* who) {
+    if (!db->has_dir || !db->has_index || (db->n_shared && (!db->d_po || !db->d_pr))) {
+        yh_set_error("%s needs the directory of the distinct hashes and the index "
+                     "(not YH_DB_NO_DIRECTORY, YH_DB_NO_INDEX or YH_DB_PAIRWISE_ONLY)", who);
+        return YH_ERR_UNSUPPORTED;
+    }
+    return YH_OK;
+}
+
+int yh_db_set_taxonomy(yh_db* db, const uint32_t* parent, const uint8_t* depth, uint32_t n_nodes, const uint32_t* leaf) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    const u64 N = db->n_refs, G = db->n_shared;
+    if (n_nodes) {  // the whole tree is checked before anything of an earlier one is touched
+        if (!parent || !depth || (N && !leaf)) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+        if (n_nodes == YH_LCA_NONE) { yh_set_error("a taxonomy holds fewer than 2^32 - 1 nodes"); return YH_ERR_INVALID_ARG; }
+        if (parent[0] != 0 || depth[0] != 0) { yh_set_error("node 0 is the root: parent[0] = 0 and depth[0] = 0"); return YH_ERR_INVALID_ARG; }
+        for (u32 v = 1; v < n_nodes; ++v) {
+            if (parent[v] >= v) { yh_set_error("parent[%u] = %u: a node's parent comes before it", v, parent[v]); return YH_ERR_INVALID_ARG; }
+            if ((u32)depth[v] != (u32)depth[parent[v]] + 1u || depth[v] > YH_LCA_MAX_DEPTH) {
+                yh_set_error("depth[%u] = %u: a node is one deeper than its parent and at most %d deep", v, (u32)depth[v], YH_LCA_MAX_DEPTH);
+                return YH_ERR_INVALID_ARG;
+            }
+        }
+        for (u64 j = 0; j < N; ++j)
+            if (leaf[j] >= n_nodes) { yh_set_error("leaf[%llu] = %u is not a node", (u64)j, leaf[j]); return YH_ERR_INVALID_ARG; }
+        YH_TRY(lca_handle_supported(db, "yh_db_set_taxonomy"));
+    }
+    YH_TRY(db_select(db));
+    YH_TRY(pipe_join(db));
+    YH_HIP(hipStreamSynchronize(db->stream));  // (an earlier taxonomy may still be read)
+    if (n_nodes == 0) {
+        yh_dfree(db, yh_lca_taxonomy_swap(db, nullptr));
+        return YH_OK;
+    }
+    // one block: parent [n_nodes] | leaf [N] | lca_shared [G] | depth [n_nodes] (the 4-byte arrays first: all stay aligned)
+    const u64 bytes = ((u64)n_nodes + N + G) * sizeof(u32) + n_nodes;
+    void* blk = nullptr;
+    if (yh_tmalloc(db, &blk, bytes) != hipSuccess) { (void)hipGetLastError(); yh_set_error("device allocation failed"); return YH_ERR_OOM; }
+    u32* const d_parent = (u32*)blk;
+    u32* const d_leaf = d_parent + n_nodes;
+    u32* const d_shared = d_leaf + N;
+    u8* const d_depth = (u8*)(d_shared + G);
+    int rc = YH_OK;
+    static const bool trace = yh_tune_flag("YH_TRACE_LCA");  // (YH_TRACE_LCA=1 behind the tuning gate: k_lca_index's device time, to stderr)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    do {
+        if (hipMemcpyAsync(d_parent, parent, (u64)n_nodes * sizeof(u32), hipMemcpyHostToDevice, db->stream) != hipSuccess ||
+            hipMemcpyAsync(d_depth, depth, n_nodes, hipMemcpyHostToDevice, db->stream) != hipSuccess ||
+            (N && hipMemcpyAsync(d_leaf, leaf, N * sizeof(u32), hipMemcpyHostToDevice, db->stream) != hipSuccess)) {
+            yh_set_error("taxonomy upload failed: %s", hipGetErrorString(hipGetLastError())); rc = YH_ERR_HIP; break;
+        }
+        if (trace && (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess)) { (void)hipGetLastError(); ev[0] = nullptr; }
+        if (trace && ev[0]) (void)hipEventRecord(ev[0], db->stream);
+        if ((rc = yh_q_lca_index(db, d_parent, d_depth, d_leaf, d_shared)) != YH_OK) break;
+        if (trace && ev[0]) (void)hipEventRecord(ev[1], db->stream);
+        if (hipStreamSynchronize(db->stream) != hipSuccess) {
+            yh_set_error("taxonomy index failed: %s", hipGetErrorString(hipGetLastError())); rc = YH_ERR_HIP; break;
+        }
+        if (trace && ev[0]) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+                fprintf(stderr, "[yh lca] k_lca_index over %llu shared hashes took %.3f ms\n", (u64)G, ms);
+        }
+    } while (0);
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    if (rc != YH_OK) { yh_tfree(db, blk); return rc; }  // (the earlier taxonomy stays)
+    YhTaxonomy t;
+    t.block = blk;
+    t.parent = d_parent; t.leaf = d_leaf; t.lca_shared = d_shared; t.depth = d_depth;
+    t.n_nodes = n_nodes;
+    t.bytes = bytes;
+    yh_dfree(db, yh_lca_taxonomy_swap(db, &t));
+    return YH_OK;
+}
+
+int yh_db_get_taxonomy(yh_db* db, uint32_t* n_nodes, uint64_t* device_bytes) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    const YhTaxonomy t = yh_lca_taxonomy(db);
+    if (n_nodes) *n_nodes = (uint32_t)t.n_nodes;
+    if (device_bytes) *device_bytes = t.bytes;
+    return YH_OK;
+}
+
+static int lca_supported(yh_db* db) {
+    YH_TRY(lca_handle_supported(db, "yh_lca"));
+    if (db->n_ghost) {
+        yh_set_error("yh_lca on a handle with ghosts: a ghost's holders belong to the rank that owns the reference");
+        return YH_ERR_UNSUPPORTED;
+    }
+    if (yh_lca_taxonomy(db).n_nodes == 0) { yh_set_error("yh_lca without a taxonomy: yh_db_set_taxonomy comes first"); return YH_ERR_UNSUPPORTED; }
+    return YH_OK;
+}
+
+int yh_lca_device(yh_db* db, const uint64_t* d_sample, const uint32_t* d_abund, uint64_t n_sample, uint32_t* d_node,
+                  uint64_t* d_counts) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    YH_TRY(lca_supported(db));
+    if (!d_counts || (n_sample && !d_sample)) { yh_set_error("null device pointer"); return YH_ERR_INVALID_ARG; }
+    YH_TRY(db_select(db));
+    YH_TRY(pipe_join(db));  // (no step context, batch slot or work list is read or written: nothing else to note)
+    return yh_q_lca(db, yh_lca_taxonomy(db), (const u64*)d_sample, d_abund, n_sample, d_node, (u64*)d_counts);
+}
+
+int yh_lca(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_t n_sample, uint32_t* node, uint64_t* counts) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    YH_TRY(lca_supported(db));
+    if (!counts || (n_sample && !sample)) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+    YH_TRY(db_select(db));
+    YH_TRY(upload_sample(db, sample, n_sample));
+    const bool looks_up = n_sample && db->n_refs && db->n_distinct;  // (otherwise: zero counts, no node written)
+    const u64 cells = 2 * yh_lca_taxonomy(db).n_nodes;
+    u32* d_a = nullptr;
+    u64* d_out = nullptr;  // the counts, then the nodes
+    int rc = YH_OK;
+    do {
+        if ((abund && yh_tmalloc(db, (void**)&d_a, std::max<u64>(n_sample, 4) * sizeof(u32)) != hipSuccess) ||
+            yh_tmalloc(db, (void**)&d_out, cells * sizeof(u64) + std::max<u64>(n_sample, 4) * sizeof(u32)) != hipSuccess) {
+            yh_set_error("device allocation failed"); rc = YH_ERR_OOM; break;
+        }
+        if (abund && n_sample && hipMemcpyAsync(d_a, abund, n_sample * sizeof(u32), hipMemcpyHostToDevice, db->stream) != hipSuccess) {
+            yh_set_error("lca upload failed"); rc = YH_ERR_HIP; break;
+        }
+        u32* const d_node = node ? (u32*)(d_out + cells) : nullptr;
+        if ((rc = yh_lca_device(db, (const uint64_t*)db->d_sample_tmp, abund ? d_a : nullptr, n_sample, d_node, (uint64_t*)d_out)) != YH_OK) break;
+        const bool down_ok = hipMemcpyAsync(counts, d_out, cells * sizeof(u64), hipMemcpyDeviceToHost, db->stream) == hipSuccess &&
+                             (!node || !looks_up || hipMemcpyAsync(node, d_node, n_sample * sizeof(u32), hipMemcpyDeviceToHost, db->stream) == hipSuccess);
+        if (!down_ok || hipStreamSynchronize(db->stream) != hipSuccess) {
+            yh_set_error("lca download failed: %s", hipGetErrorString(hipGetLastError()));
+            rc = YH_ERR_HIP;
+        }
+    } while (0);
+    yh_tfree(db, d_a); yh_tfree(db, d_out);
     return rc;
 }
 

@@ -1,0 +1,32 @@
+// yh_lca.h — the lowest-common-ancestor classification of sample hashes (yh_lca.hip) as yh_api.hip calls it.  Internal, like
+// yh_common.h.
+#pragma once
+
+#include "yh_common.h"
+
+// The taxonomy of a handle (yh_db_set_taxonomy): one block from the buffer cache and the four arrays inside it.  It is kept
+// in a table beside the handles (yh_lca.hip), keyed by the handle, not in yh_db itself: yh_common.h is part of the source the
+// PMC traffic files of the run and train kernels are pinned to (profiles/traffic_r06_*.json: source_tag), and a feature that
+// touches neither kernel leaves that source, and with it the benchmark's roofline figures, as they are.
+struct YhTaxonomy {
+    void* block = nullptr;
+    const u32* parent = nullptr;      // [n_nodes]
+    const u32* leaf = nullptr;        // [N] the node of reference j
+    const u32* lca_shared = nullptr;  // [G] the LCA of the leaves of shared hash gi's holders (k_lca_index)
+    const u8* depth = nullptr;        // [n_nodes]
+    u64 n_nodes = 0, bytes = 0;       // (0 nodes: no taxonomy set)
+};
+// the handle's taxonomy (n_nodes == 0: none set)
+YhTaxonomy yh_lca_taxonomy(const yh_db* db);
+// Install `t` as the handle's taxonomy (null: remove it).  Returns the block of the one it replaces (or null) for the caller
+// to free once nothing reads it any more.  yh_db_destroy removes the entry with the handle.
+void* yh_lca_taxonomy_swap(const yh_db* db, const YhTaxonomy* t);
+
+// d_lca_shared[gi] = LCA of d_leaf[holder] over the posting list of shared hash gi, for every gi in [0, db->n_shared), enqueued
+// on the handle's stream (yh_db_set_taxonomy).  The tree has passed the host's validation; n_shared == 0 launches nothing.
+int yh_q_lca_index(yh_db* db, const u32* d_parent, const u8* d_depth, const u32* d_leaf, u32* d_lca_shared);
+
+// node [n_sample] (d_node may be null: counts only) and counts [n_nodes][2] of one sample against taxonomy `t` of the handle,
+// enqueued on the handle's stream (include/yacht_hip.h: yh_lca_device).  d_abund may be null: every abundance is 1.  The
+// caller has checked the handle, its taxonomy and the pointers.
+int yh_q_lca(yh_db* db, const YhTaxonomy& t, const u64* d_sample, const u32* d_abund, u64 n_sample, u32* d_node, u64* d_counts);

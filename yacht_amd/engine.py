@@ -373,6 +373,58 @@ class RefDB:
         _lib.check(self._lib.yh_explain_device(self._h, C.c_void_p(d_sample), C.c_void_p(d_abund), n_sample, C.c_void_p(d_member),
                                                C.c_void_p(d_flags), C.c_void_p(d_totals)))
 
+    def set_taxonomy(self, parent, depth, leaf) -> None:
+        """Hang the references in a taxonomy (yh_db_set_taxonomy): parent uint32 [n_nodes] with parent[0] = 0 and parent[v] <
+        v, depth uint8 [n_nodes] with depth[v] = depth[parent[v]] + 1 <= 16, leaf uint32 [n_refs] the node of every reference
+        (an internal node or the root, 0, are allowed).  Synchronous; replaces an earlier taxonomy; parent=None (or no
+        node) removes it.  A tree the library refuses raises YachtHipError (YH_ERR_INVALID_ARG) and the earlier one stays."""
+        if parent is None or np.asarray(parent).size == 0:
+            _lib.check(self._lib.yh_db_set_taxonomy(self._h, None, None, 0, None))
+            return
+        parent, depth, leaf = np.asarray(parent), np.asarray(depth), np.asarray(leaf)
+        if parent.ndim != 1 or depth.shape != parent.shape:
+            raise ValueError(f"parent and depth must hold one entry per node: {list(parent.shape)} and {list(depth.shape)}")
+        if leaf.ndim != 1 or leaf.size != self.n_refs:
+            raise ValueError(f"leaf must hold one node per reference: {leaf.size} entries for {self.n_refs} references")
+        for name, a, top in (("parent", parent, 0xFFFFFFFF), ("depth", depth, 0xFF), ("leaf", leaf, 0xFFFFFFFF)):
+            if a.dtype.kind not in "iu":
+                raise ValueError(f"{name} must be integers, not {a.dtype}")
+            if a.size and (int(a.min()) < 0 or int(a.max()) > top):
+                raise ValueError(f"{name} must lie in [0, {top}]")
+        if parent.size >= 0xFFFFFFFF:
+            raise ValueError("a taxonomy holds fewer than 2**32 - 1 nodes")
+        parent = np.ascontiguousarray(parent, dtype=np.uint32)
+        depth = np.ascontiguousarray(depth, dtype=np.uint8)
+        leaf = np.ascontiguousarray(leaf, dtype=np.uint32)
+        _lib.check(self._lib.yh_db_set_taxonomy(self._h, _ptr(parent), _ptr(depth), parent.size, _ptr(leaf)))
+
+    def taxonomy_info(self) -> dict:
+        """{"n_nodes": nodes of the taxonomy set (0: none), "device_bytes": what its arrays take} (yh_db_get_taxonomy)."""
+        n, b = C.c_uint32(0), C.c_uint64(0)
+        _lib.check(self._lib.yh_db_get_taxonomy(self._h, C.byref(n), C.byref(b)))
+        return {"n_nodes": int(n.value), "device_bytes": int(b.value)}
+
+    def lca(self, sample, abund=None, want_nodes: bool = True) -> Tuple[Optional[np.ndarray], np.ndarray]:
+        """Every sample hash classified by the lowest common ancestor of its holders in the taxonomy (yh_lca).  abund: one
+        abundance per sample hash, or None (all 1).  Returns (nodes, counts): nodes uint32 [n], _lib.YH_LCA_NONE for a hash
+        no reference holds, else the node of its only holder or the LCA of all of them (None with want_nodes=False: the
+        counts only); counts uint64 [n_nodes, 2], per node the number of sample hashes that resolve exactly there and the sum
+        of their abundances (direct assignments: taxonomy.clade_sums adds the subtrees)."""
+        if abund is None:
+            sample = _as_u64(sample)
+        else:
+            sample, abund = check_abundances(sample, abund)
+        nodes = np.full(sample.size, _lib.YH_LCA_NONE, dtype=np.uint32) if want_nodes else None
+        counts = np.zeros((self.taxonomy_info()["n_nodes"], 2), dtype=np.uint64)
+        _lib.check(self._lib.yh_lca(self._h, _ptr(sample), _ptr(abund), sample.size, _ptr(nodes), _ptr(counts)))
+        return nodes, counts
+
+    def lca_device(self, d_sample: int, d_abund: int, n_sample: int, d_node: int, d_counts: int) -> None:
+        """yh_lca_device: uint64 sample and uint32 abundances (0: all 1) in, uint32 [n_sample] nodes (0: none) and uint64
+        [n_nodes][2] counts out."""
+        _lib.check(self._lib.yh_lca_device(self._h, C.c_void_p(d_sample), C.c_void_p(d_abund), n_sample, C.c_void_p(d_node),
+                                           C.c_void_p(d_counts)))
+
     def gather(self, sample, cand, abund=None, min_hits: int = 1, cap_rows: Optional[int] = None, want_owner: bool = False):
         """The candidates ranked by the sample hashes each adds (yh_gather): round after round the candidate holding the
         most sample hashes nobody owns yet (ties: the smallest index) takes them.  cand: one byte per reference, non-zero =

@@ -72,6 +72,13 @@ ARGUMENTS = (
     ("--gather_top", dict(type=int, default=None,
                           help="Rank at most this many organisms per sample and coverage (with --gather; default: no bound).  "
                                "A cohort needs it, at most %d: its samples are ranked a block at a time on the device." % _lib.YH_GATHER_BATCH_MAX_ROWS)),
+    ("--lineages", dict(type=str, default=None,
+                        help="A lineage table of the reference organisms, the CSV sourmash's tax and lca commands take "
+                             "(ident,superkingdom,phylum,class,order,family,genus,species[,strain]; an ident is an organism's name "
+                             "or its first word).  Every sample hash is then classified by the lowest common ancestor of the "
+                             "organisms that hold it: results/lca_summary.tsv, per taxon the sample hashes and abundance that "
+                             "resolve exactly there and anywhere under it, and how many of its organisms were called present.  "
+                             "One sample file.")),
 )
 
 # messages the reference raises with (callers and its tests match on them)
@@ -166,6 +173,11 @@ def main(args) -> None:
 
         gather_plan = gather.gather_options(args, len(files))  # (ValueError before anything is written or any device work)
         gather_cap = gather.gather_top(args, len(files))
+    lineages = None
+    if getattr(args, "lineages", None) is not None:
+        from . import taxonomy
+
+        lineages = taxonomy.lineages_option(args, len(files))  # (ValueError before anything is written or any device work)
     if len(files) > 1:
         from . import cohort
 
@@ -240,6 +252,15 @@ def main(args) -> None:
             gather_sets = [all_sets[all_covs.index(c)] for c in gather_plan[0]]
             gather_rows = gather.gather_call_sets(hr._LAST_RUN["db"], hr._LAST_RUN["mins"],
                                                   _residual.sample_abundances_or_none(sample_sig), gather_sets, gather_plan[1], gather_cap)
+    if lineages is not None:  # one taxonomy and one call on the still-resident database (references in manifest order)
+        from . import residual as _residual
+
+        with phases.phase("lca"):
+            tree = taxonomy.build_tree(manifest["organism_name"], lineages)
+            hr._LAST_RUN["db"].set_taxonomy(*tree[:3])
+            lca_abund = _residual.sample_abundances_or_none(sample_sig)
+            _, lca_counts = hr._LAST_RUN["db"].lca(hr._LAST_RUN["mins"], lca_abund, want_nodes=False)
+            lca_sets = _residual.call_sets_of(manifest["organism_name"], results if has_raw else results[1:])
     hr.release_reference_dbs()
     results = trim_results(results)
 
@@ -253,6 +274,11 @@ def main(args) -> None:
         residual.write_outputs(results_folder, sample_sig, user_covs, call_sets, *explained, residual_cov)
     if gather_plan is not None:
         gather.write_profile(results_folder, sample_sig, gather_plan[0], gather_rows, manifest["organism_name"])
+    if lineages is not None:
+        n_hashes = len(sample_sig.minhash)
+        taxonomy.write_summary(results_folder, taxonomy.summary_frame(
+            tree[0], tree[2], tree[3], lca_counts, n_hashes, n_hashes if lca_abund is None else int(sum(int(a) for a in lca_abund)),
+            covs if has_raw else covs[1:], lca_sets))
     _t_write.__exit__(None, None, None)
 
 
