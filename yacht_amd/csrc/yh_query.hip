@@ -175,29 +175,52 @@ __global__ void __launch_bounds__(256) k_reduce_replicas(u32* __restrict__ reps,
 // The reducer of the fused launch: RPT references per thread, all their reads in flight together, ONE scan and ONE
 // atomic per workgroup for the work list -- a workgroup covers RPT x blockDim references in one pass (the launch has
 // only the lookup's spare wave slots for this role: looping over 1024-reference blocks serialized five round trips).
+constexpr int FUSED_MAX_REPS = 4;   // replicas of the fused step's counters at most (yh_q_step_fused)
+// references whose reads a thread requests as one group (1: 61 VGPRs, and the compiler issues the next reference's reads
+// while the last one's arrive; 2: 64 VGPRs and 120 bytes of scratch per lane in the 1024-lane kernels)
+constexpr int FUSED_RED_GROUP = 1;
 template <int RPT>
 __device__ __forceinline__ void reduce_replicas_multi(u32 blk, u32* lds, u32* __restrict__ reps, u32 R, u64 n, u32* __restrict__ out,
                                                       u32* __restrict__ maskbits, const FusedRun& f) {
     const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+    // Everything a thread reads of a reference is in flight together: the replica loop has a compile-time bound and every
+    // read is branch-free (clamped index, the value dropped afterwards).  With the run-time bound R and a branch per
+    // reference the compiler waited for each reference's record offsets and then for every replica's pair of reads in
+    // turn -- 20 dependent trips per workgroup, each queued behind the lookups' 10^6 random reads: 23.6 us until a
+    // workgroup's reads were back, the reducer the last role to end in 49 launches of 50, 2.6 us behind the last lookup.
+    // Now 7.3 us, the role ends 7 us before the launch does (profiles/fused_roles/timeline.txt).
+    static_assert(RPT % FUSED_RED_GROUP == 0, "references per thread: whole groups");
     u64 j[RPT];
     u32 acc[RPT], acc2[RPT], size_j[RPT], nsh[RPT], rpo0[RPT], rpo1[RPT];
 #pragma unroll
-    for (int r = 0; r < RPT; ++r) {
-        j[r] = ((u64)blk * RPT + r) * blockDim.x + threadIdx.x;
-        acc[r] = acc2[r] = size_j[r] = nsh[r] = rpo0[r] = rpo1[r] = 0;
-        if (j[r] < n) {
-            size_j[r] = f.sizes[j[r]];
-            nsh[r] = f.nshared[j[r]];
-            if (f.work) { rpo0[r] = f.rpo[j[r]]; rpo1[r] = f.rpo[j[r] + 1]; }
+    for (int r = 0; r < RPT; ++r) j[r] = ((u64)blk * RPT + r) * blockDim.x + threadIdx.x;
+#pragma unroll
+    for (int r0 = 0; r0 < RPT; r0 += FUSED_RED_GROUP) {
+        u32 t1[FUSED_RED_GROUP][FUSED_MAX_REPS], t2[FUSED_RED_GROUP][FUSED_MAX_REPS];
+#pragma unroll
+        for (int d = 0; d < FUSED_RED_GROUP; ++d) {
+            const u32 jj = (u32)min(j[r0 + d], n - 1);  // (a uniform base and a 32-bit index per read: no address pairs in registers)
+            size_j[r0 + d] = f.sizes[jj];
+            nsh[r0 + d] = f.nshared[jj];
+            rpo0[r0 + d] = f.work ? f.rpo[jj] : 0u;
+            rpo1[r0 + d] = f.work ? f.rpo[jj + 1u] : 0u;
+#pragma unroll
+            for (u32 k = 0; k < (u32)FUSED_MAX_REPS; ++k) {
+                const u64 row = (u64)min(k, R - 1u) * n;
+                t1[d][k] = (reps + row)[jj];
+                t2[d][k] = (f.reps2 + row)[jj];
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < FUSED_RED_GROUP; ++d) {
+            const int r = r0 + d;
+            acc[r] = acc2[r] = 0;
+#pragma unroll
+            for (u32 k = 0; k < (u32)FUSED_MAX_REPS; ++k)
+                if (j[r] < n && k < R) { acc[r] += t1[d][k]; acc2[r] += t2[d][k]; }
+            if (j[r] >= n) size_j[r] = nsh[r] = rpo0[r] = rpo1[r] = 0;
         }
     }
-#pragma unroll
-    for (int r = 0; r < RPT; ++r)
-        if (j[r] < n)
-            for (u32 k = 0; k < R; ++k) {
-                acc[r] += reps[(u64)k * n + j[r]];
-                acc2[r] += f.reps2[(u64)k * n + j[r]];
-            }
 #pragma unroll
     for (int r = 0; r < RPT; ++r) {
         if (j[r] < n) {
@@ -1076,6 +1099,7 @@ __device__ __forceinline__ void stage_subset_bits(u32* lmask, const ExclPieces& 
 
 // (body: any workgroup size that is a multiple of 64; `wg` of `n_wgs` workgroups walk the work list, a fixed share each;
 // lmask: n_mask_words of LDS when LDSMASK)
+// Any n_wgs >= 1 walks the whole list (stride n_wgs * WPB): the grid's size only decides how many rounds that takes.
 template <bool LDSMASK, int U = EXCL_U>
 __device__ __forceinline__ void excl_pieces_body(u32 wg, u32 n_wgs, u32* lmask, const ExclPieces& q) {
     const u32 WPB = blockDim.x >> 6;
@@ -1103,7 +1127,10 @@ __global__ void __launch_bounds__(EXCL_PIECE_THREADS) k_excl_pieces(const ExclPi
 // CONSECUTIVE samples share one launch: workgroups [0, E) run the exclusive pass of sample k - 2, the next R the reducer
 // of sample k - 1, the rest the lookup of sample k -- no workgroup depends on another of the same launch: consecutive
 // samples alternate between two sets of replica counters and rotate through three step contexts (subset bits + work
-// list).  The short roles come first in dispatch order, and a step costs one launch: the lookup's.
+// list).  The short roles come first in dispatch order, and a step costs one launch: the lookup's -- measured per
+// workgroup (profiles/fused_roles/timeline.txt): the last workgroup to end is a lookup one in 50 launches of 50, the
+// launch spans 30.1 us against 30.7 for the stand-alone lookup kernel.  (Until the reducer's reads were put in flight
+// together -- reduce_replicas_multi -- it was the reducer, and the two side roles cost the launch 2.6 us.)
 struct StepFused {
     TileLookup look;   u32 look_wgs;
     u32* r_reps; u32 r_R; u64 r_n; u32* r_out; u32* r_maskbits; FusedRun r_fused; u32 red_wgs;
@@ -1112,7 +1139,9 @@ struct StepFused {
 // (8 waves per SIMD = two workgroups per CU, as the stand-alone lookup has: 64 VGPRs; the exclusive role unrolls by 2.)
 // Dispatch order = block order: the exclusive role's workgroups come first (most of them find nothing beyond the work
 // list's end and are gone after one read), then the reducer's -- 4 references per thread, 21 workgroups for 85 205
-// references: it fits the wave slots the 488 lookup workgroups of a 10^6-hash sample leave free -- then the lookup's.
+// references: it fits the wave slots the 489 lookup workgroups of a 10^6-hash sample leave free -- then the lookup's.
+// The other two orders (reducer, lookup, exclusive; lookup, reducer, exclusive) measure the same: 31.7 us per step each
+// (with the exclusive role cut to the 10-21 workgroups its lists need; that sizing bought nothing either: yh_q_step_fused).
 // (Tried and dropped: no dedicated exclusive workgroups, every workgroup walking its share of the work list BEHIND its own
 // job -- the pass then starts when the lookups end instead of beside them: 49.8 us per launch against 33; and claiming
 // records from a shared cursor, which hung the device on a non-uniform early exit before a barrier.)
@@ -1434,7 +1463,9 @@ int yh_q_step_fused(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_overlap
     const u64 N = db->n_refs;
     u32 R;
     YH_TRY(ensure_reps(db, R));
-    while (R > 1 && R > 4u) R >>= 1;
+    // (four replicas, re-measured inside the fused launch with the reducer's reads in flight together: two 37.1 us per step
+    // against 31.7, one 49.4; the real-shape leg 13.6 / 13.9 / 13.6 us with two / four / one: no difference)
+    while (R > 1 && R > (u32)FUSED_MAX_REPS) R >>= 1;
     // One geometry per launch: the sample's size picks it (as for the stand-alone lookup: yh_tile_shape_for); a draining
     // launch takes the small one.
     const YhTileShape shape = d_sample ? yh_tile_shape_for(n_sample) : yh_tile_shape(0);
@@ -1444,7 +1475,13 @@ int yh_q_step_fused(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_overlap
     if (db->pend_excl >= 0) {   // exclusive pass of the step reduced by the previous launch
         const int c = db->pend_excl;
         s.excl = excl_args(db, db->ctx_count[c], db->ctx_work[c], db->ctx_bits[c], nullptr, db->pend_excl_out, nullptr, nullptr, true);
-        s.excl_wgs = std::min<u32>((db->n_chunks + waves - 1) / waves, 4096u / waves);  // (most find nothing and leave after one read)
+        // Sized for every piece of the database; most workgroups find nothing and leave after one read (1.0 us in their slot).
+        // Any size >= 1 is exact (the role strides over the list).  Sizing it by the lists recent steps produced -- 10 to 21
+        // workgroups instead of 256 on the bench shape -- was built and dropped: 31.7 against 32.0 us per step, inside the
+        // run-to-run spread of 0.5 (profiles/fused_roles/compare.txt).  YH_FUSED_EXCL_WGS: tests force the role's size.
+        static const u32 wgs_env = (u32)yh_tune_int("YH_FUSED_EXCL_WGS", 0);
+        s.excl_wgs = std::min<u32>((db->n_chunks + waves - 1) / waves, 4096u / waves);
+        if (wgs_env) s.excl_wgs = std::max<u32>(std::min<u32>(wgs_env, s.excl_wgs), 1u);
         s.excl_lds = s.excl.n_mask_words <= EXCL_LDS_WORDS ? 1u : 0u;
         if (s.excl_lds) lds_words = std::max(lds_words, s.excl.n_mask_words);
     }
