@@ -172,75 +172,101 @@ __global__ void __launch_bounds__(256) k_reduce_replicas(u32* __restrict__ reps,
     reduce_replicas_body(blockIdx.x, lds, reps, R, n, out, mask, maskbits, excl3, fused);
 }
 
-// The reducer of the fused launch: RPT references per thread, all their reads in flight together, ONE scan and ONE
-// atomic per workgroup for the work list -- a workgroup covers RPT x blockDim references in one pass (the launch has
-// only the lookup's spare wave slots for this role: looping over 1024-reference blocks serialized five round trips).
-constexpr int FUSED_MAX_REPS = 4;   // replicas of the fused step's counters at most (yh_q_step_fused)
-// references whose reads a thread requests as one group (1: 61 VGPRs, and the compiler issues the next reference's reads
-// while the last one's arrive; 2: 64 VGPRs and 120 bytes of scratch per lane in the 1024-lane kernels)
-constexpr int FUSED_RED_GROUP = 1;
+// The reducer of the fused launch: RPT references per thread, ONE scan and ONE atomic per workgroup for the work list -- a
+// workgroup covers RPT x blockDim references in one pass (the launch has only the lookup's spare wave slots for this role).
+constexpr int FUSED_MAX_REPS = 16;  // replicas of the fused step's counters at most (yh_q_step_fused)
+constexpr u32 FUSED_REPS_FORM1 = 8, FUSED_REPS_FORM2 = 8;  // rows by lookup geometry <1, 1024, 10> / <2, 1024, 10>, measured: yh_q_step_fused
+// (a uniform base and a 32-bit byte offset per read, where base[index] computes an address pair per read in flight)
+__device__ __forceinline__ u32 word_at(const u32* base, u32 byte_off) {
+    return *reinterpret_cast<const u32*>(reinterpret_cast<const char*>(base) + byte_off);
+}
+// acc[r] += the R replica rows of one counter set at RPT references, G rows x RPT references requested together: the loop
+// over the rows of a group has a compile-time bound and every read is branch-free (clamped row, clamped index, the value
+// masked afterwards -- a mask and not a branch: the compiler moves a read whose value only a branch uses INTO that branch,
+// and the reads of a group then wait for each other).  The run-time loop is the one over groups: R / G trips.
+template <int RPT, int G>
+__device__ __forceinline__ void sum_replica_rows(const u32* set, u32 R, u64 n, const u32 (&off)[RPT], const bool (&ok)[RPT],
+                                                 u32 (&acc)[RPT]) {
+#pragma unroll 1
+    for (u32 g = 0; g < R; g += (u32)G) {
+        u32 t[RPT][G];
+#pragma unroll
+        for (u32 k = 0; k < (u32)G; ++k) {
+            const u64 row = (u64)min(g + k, R - 1u) * n;
+#pragma unroll
+            for (int r = 0; r < RPT; ++r) t[r][k] = word_at(set + row, off[r]);
+        }
+#pragma unroll
+        for (u32 k = 0; k < (u32)G; ++k)
+#pragma unroll
+            for (int r = 0; r < RPT; ++r) acc[r] += t[r][k] & ((ok[r] && g + k < R) ? ~0u : 0u);
+    }
+}
 template <int RPT>
 __device__ __forceinline__ void reduce_replicas_multi(u32 blk, u32* lds, u32* __restrict__ reps, u32 R, u64 n, u32* __restrict__ out,
                                                       u32* __restrict__ maskbits, const FusedRun& f) {
     const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    // Everything a thread reads of a reference is in flight together: the replica loop has a compile-time bound and every
-    // read is branch-free (clamped index, the value dropped afterwards).  With the run-time bound R and a branch per
-    // reference the compiler waited for each reference's record offsets and then for every replica's pair of reads in
-    // turn -- 20 dependent trips per workgroup, each queued behind the lookups' 10^6 random reads: 23.6 us until a
-    // workgroup's reads were back, the reducer the last role to end in 49 launches of 50, 2.6 us behind the last lookup.
-    // Now 7.3 us, the role ends 7 us before the launch does (profiles/fused_roles/timeline.txt).
-    static_assert(RPT % FUSED_RED_GROUP == 0, "references per thread: whole groups");
-    u64 j[RPT];
+    // The launch is bound by the rate of its L2 requests (the lookups' 1.27 x 10^6 isolated reads), so every request of
+    // this role is paid for in full -- a timing-only build without the role: 1.2 us of the step at four rows and 1.4 at eight
+    // while it read every row of both sets, the sizes and the record offsets of every reference -- and a
+    // dependent read here queues behind 10^6 random ones (with a run-time row bound inside the group and a branch per
+    // reference: 20 dependent trips per workgroup, 23.6 us until a workgroup's reads were back, the reducer the last role
+    // to end in 49 launches of 50).  So: the first set's rows, up to eight per trip for all RPT references; everything
+    // else -- the second set's rows (a hit on a shared hash is a hit, so they are zero where the first set's are), the
+    // sizes and record offsets, the clearing -- only in lanes that hold a hit reference, under 1 % of the references of a
+    // step and a fifth of the waves.  (Unconditional clearing: R x 0.68 MB per step written for nothing.)
+    // (a reference's index as a uniform base and a 32-bit lane part, clamped for the reads; whether it exists as a lane mask)
+    const u64 j0 = (u64)blk * RPT * blockDim.x + threadIdx.x;
+    u32 jj[RPT], off[RPT];
+    bool ok[RPT];
     u32 acc[RPT], acc2[RPT], size_j[RPT], nsh[RPT], rpo0[RPT], rpo1[RPT];
 #pragma unroll
-    for (int r = 0; r < RPT; ++r) j[r] = ((u64)blk * RPT + r) * blockDim.x + threadIdx.x;
+    for (int r = 0; r < RPT; ++r) {
+        ok[r] = j0 + (u64)r * blockDim.x < n;
+        jj[r] = (u32)min(j0 + (u64)r * blockDim.x, n - 1);
+        off[r] = jj[r] * 4u;  // (fits: yh_q_step_fused_ok)
+        acc[r] = acc2[r] = size_j[r] = nsh[r] = rpo0[r] = rpo1[r] = 0;
+    }
+    if (R >= 8u) sum_replica_rows<RPT, 8>(reps, R, n, off, ok, acc);
+    else sum_replica_rows<RPT, 4>(reps, R, n, off, ok, acc);
+    // (a wave with a hit holds one or two as a rule: one reference at a time, its reads -- eight rows, sizes, record offsets -- together)
 #pragma unroll
-    for (int r0 = 0; r0 < RPT; r0 += FUSED_RED_GROUP) {
-        u32 t1[FUSED_RED_GROUP][FUSED_MAX_REPS], t2[FUSED_RED_GROUP][FUSED_MAX_REPS];
-#pragma unroll
-        for (int d = 0; d < FUSED_RED_GROUP; ++d) {
-            const u32 jj = (u32)min(j[r0 + d], n - 1);  // (a uniform base and a 32-bit index per read: no address pairs in registers)
-            size_j[r0 + d] = f.sizes[jj];
-            nsh[r0 + d] = f.nshared[jj];
-            rpo0[r0 + d] = f.work ? f.rpo[jj] : 0u;
-            rpo1[r0 + d] = f.work ? f.rpo[jj + 1u] : 0u;
-#pragma unroll
-            for (u32 k = 0; k < (u32)FUSED_MAX_REPS; ++k) {
-                const u64 row = (u64)min(k, R - 1u) * n;
-                t1[d][k] = (reps + row)[jj];
-                t2[d][k] = (f.reps2 + row)[jj];
-            }
-        }
-#pragma unroll
-        for (int d = 0; d < FUSED_RED_GROUP; ++d) {
-            const int r = r0 + d;
-            acc[r] = acc2[r] = 0;
-#pragma unroll
-            for (u32 k = 0; k < (u32)FUSED_MAX_REPS; ++k)
-                if (j[r] < n && k < R) { acc[r] += t1[d][k]; acc2[r] += t2[d][k]; }
-            if (j[r] >= n) size_j[r] = nsh[r] = rpo0[r] = rpo1[r] = 0;
+    for (int r = 0; r < RPT; ++r) {
+        if (acc[r]) {  // (ok[r], and jj is the reference's own index)
+            const u32 off1[1] = {off[r]};
+            const bool ok1[1] = {true};
+            u32 a2[1] = {0u};
+            size_j[r] = f.sizes[jj[r]];
+            nsh[r] = f.nshared[jj[r]];
+            rpo0[r] = f.work ? f.rpo[jj[r]] : 0u;
+            rpo1[r] = f.work ? f.rpo[jj[r] + 1u] : 0u;
+            sum_replica_rows<1, 8>(f.reps2, R, n, off1, ok1, a2);
+            acc2[r] = a2[0];
+            for (u32 k = 0; k < R; ++k) (reps + (u64)k * n)[jj[r]] = 0;
+            if (acc2[r])
+                for (u32 k = 0; k < R; ++k) (f.reps2 + (u64)k * n)[jj[r]] = 0;
         }
     }
 #pragma unroll
     for (int r = 0; r < RPT; ++r) {
-        if (j[r] < n) {
-            for (u32 k = 0; k < R; ++k) { reps[(u64)k * n + j[r]] = 0; f.reps2[(u64)k * n + j[r]] = 0; }
-            out[j[r]] = acc[r];
-            f.n_match[j[r]] = acc[r] - acc2[r];
-            if (f.n_excl) f.n_excl[j[r]] = acc[r] ? size_j[r] - nsh[r] : 0u;
+        if (ok[r]) {
+            out[jj[r]] = acc[r];
+            f.n_match[jj[r]] = acc[r] - acc2[r];
+            if (f.n_excl) f.n_excl[jj[r]] = acc[r] ? size_j[r] - nsh[r] : 0u;
         }
         const u64 bal = __ballot(acc[r] != 0);
-        if (lane == 0 && (j[r] >> 5) < ((n + 255) / 256) * 8) {  // (whole 256-reference blocks: what the arrays are sized for)
-            maskbits[(j[r] >> 5)] = (u32)bal;
-            maskbits[(j[r] >> 5) + 1] = (u32)(bal >> 32);
-            if (f.bits_out) { f.bits_out[(j[r] >> 5)] = (u32)bal; f.bits_out[(j[r] >> 5) + 1] = (u32)(bal >> 32); }
+        const u64 jr = j0 + (u64)r * blockDim.x;
+        if (lane == 0 && (jr >> 5) < ((n + 255) / 256) * 8) {  // (whole 256-reference blocks: what the arrays are sized for)
+            maskbits[(jr >> 5)] = (u32)bal;
+            maskbits[(jr >> 5) + 1] = (u32)(bal >> 32);
+            if (f.bits_out) { f.bits_out[(jr >> 5)] = (u32)bal; f.bits_out[(jr >> 5) + 1] = (u32)(bal >> 32); }
         }
     }
     if (!f.work) return;
     u32 np[RPT], mine = 0;
 #pragma unroll
     for (int r = 0; r < RPT; ++r) {
-        const bool in = acc[r] != 0 && j[r] < f.work_refs;
+        const bool in = acc[r] != 0 && jj[r] < f.work_refs;
         np[r] = in ? (rpo1[r] - rpo0[r] + (u32)EXCL_PIECE_C - 1u) / (u32)EXCL_PIECE_C : 0u;
         mine += np[r];
     }
@@ -265,7 +291,7 @@ __device__ __forceinline__ void reduce_replicas_multi(u32 blk, u32* lds, u32* __
         const u32 last = rpo1[r];
         for (u32 i = 0; i < np[r]; ++i) {
             const u32 first = rpo0[r] + i * (u32)EXCL_PIECE_C;
-            f.work[at + i] = make_uint4((u32)j[r], first, min(first + (u32)EXCL_PIECE_C, last), 0u);
+            f.work[at + i] = make_uint4(jj[r], first, min(first + (u32)EXCL_PIECE_C, last), 0u);
         }
         at += np[r];
     }
@@ -1157,11 +1183,9 @@ __global__ void __launch_bounds__(THREADS, THREADS == 1024 ? 8 : 4) k_step_fused
     }
     b -= s.excl_wgs;
     if (b < s.red_wgs) {
-        const u32 blocks = (u32)((s.r_n + 4ull * THREADS - 1) / (4ull * THREADS));
-        for (u32 blk = b; blk < blocks; blk += s.red_wgs) {
-            reduce_replicas_multi<4>(blk, smem, s.r_reps, s.r_R, s.r_n, s.r_out, s.r_maskbits, s.r_fused);
-            __syncthreads();  // (the scan words in LDS are re-used by the next block)
-        }
+        // (one block of 4 x THREADS references per workgroup: yh_q_step_fused sizes the role so; a loop over blocks here made
+        // the compiler carry the lane predicates of the scan across it in registers the reads need)
+        reduce_replicas_multi<4>(b, smem, s.r_reps, s.r_R, s.r_n, s.r_out, s.r_maskbits, s.r_fused);
         return;
     }
     b -= s.red_wgs;
@@ -1456,19 +1480,31 @@ int yh_q_overlap_indexed(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_ov
 // The caller has checked yh_q_step_fused_ok and allocated the step contexts 0..2.
 bool yh_q_step_fused_ok(const yh_db* db, u64 n_sample) {
     return db->has_dir && db->has_index && db->d_cbkt && fused_possible(db, reinterpret_cast<const u32*>(db), true) &&
-           db->n_chunks && !db->n_ghost && n_sample >= 1 && n_sample <= 0xfffffff0ull;
+           db->n_chunks && !db->n_ghost && n_sample >= 1 && n_sample <= 0xfffffff0ull &&
+           db->n_refs < (1ull << 30);  // (the reducer role's 32-bit byte offsets into a row of counters)
 }
 int yh_q_step_fused(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_overlap, u32* d_excl, u32* d_match) {
     hipStream_t st = db->stream;
     const u64 N = db->n_refs;
     u32 R;
     YH_TRY(ensure_reps(db, R));
-    // (four replicas, re-measured inside the fused launch with the reducer's reads in flight together: two 37.1 us per step
-    // against 31.7, one 49.4; the real-shape leg 13.6 / 13.9 / 13.6 us with two / four / one: no difference)
-    while (R > 1 && R > (u32)FUSED_MAX_REPS) R >>= 1;
     // One geometry per launch: the sample's size picks it (as for the stand-alone lookup: yh_tile_shape_for); a draining
     // launch takes the small one.
     const YhTileShape shape = d_sample ? yh_tile_shape_for(n_sample) : yh_tile_shape(0);
+    // Replica rows the LOOKUP of this launch counts into, by its geometry, at most what ensure_reps allocated.  The flush of
+    // a tile's hit table is one device-scope add per (workgroup, reference); ~420 of the 489 workgroups of a 10^6-hash sample
+    // add to the same counter of a present genome within a few us, and the adds of one address are serialized memory-side.
+    // The stand-alone lookup of that shape: 47.7 / 35.8 / 30.4 / 28.7 / 28.7 us with 1 / 2 / 4 / 8 / 16 rows; the fused step
+    // 49.2 / 37.2 / 31.3 / 30.4 / 31.3 us (sixteen rows cost the reducer role what they save the lookup), a 4 x 10^5-hash
+    // sample (1024-lane tiles of one hash) 22.2 / 21.5 / 22.9 us with 4 / 8 / 16 (profiles/fused_replicas/sweep.txt): eight
+    // for both.  The 256-lane geometry has no hot counter (the real-shape leg: 13.6 / 13.9 / 13.6 us with two / four /
+    // one) and every extra row only costs its reducer: four stay there.
+    // The count travels with the pending step (pend_red_parity): the reducer of the NEXT launch, whatever its geometry,
+    // sums and clears exactly these rows.  YH_FUSED_REPS (debug tuning): sweeps and tests force the count.
+    static const u32 reps_env = (u32)std::max<long long>(yh_tune_int("YH_FUSED_REPS", 0), 0);
+    static const u32 fused_reps[3] = {4u, FUSED_REPS_FORM1, FUSED_REPS_FORM2};
+    const u32 r_want = std::min<u32>(reps_env ? reps_env : fused_reps[shape.form], (u32)FUSED_MAX_REPS);
+    while (R > 1 && R > r_want) R >>= 1;
     const u32 threads = shape.threads, waves = threads / 64, tslots = 1u << shape.tbits;
     StepFused s{};
     u32 lds_words = 3 * tslots;  // the lookup role's hit table
@@ -1487,15 +1523,16 @@ int yh_q_step_fused(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_overlap
     }
     if (db->pend_red >= 0) {    // reducer of the step looked up by the previous launch
         const int c = db->pend_red;
-        u32* const reps1 = db->d_reps + (u64)db->pend_red_parity * 2 * db->reps_cap;
+        // (pend_red_parity: bit 0 the counter set, the bits above it the rows the step's lookup counted into)
+        u32* const reps1 = db->d_reps + (u64)(db->pend_red_parity & 1) * 2 * db->reps_cap;
         s.r_reps = reps1;
-        s.r_R = R;
+        s.r_R = (u32)db->pend_red_parity >> 1;
         s.r_n = N;
         s.r_out = db->pend_red_out[0];
         s.r_maskbits = db->ctx_bits[c];
         s.r_fused = FusedRun{reps1 + db->reps_cap, db->d_sizes, db->d_nshared, db->pend_red_out[1], db->pend_red_out[2], nullptr,
                              db->d_hpo, db->ctx_work[c], db->ctx_count[c], (u32)N};
-        s.red_wgs = (u32)((N + 4ull * threads - 1) / (4ull * threads));  // (4 references per thread)
+        s.red_wgs = (u32)((N + 4ull * threads - 1) / (4ull * threads));  // (4 references per thread, ONE block per workgroup: the role does not loop)
     }
     int c_new = -1;
     if (d_sample) {
@@ -1522,7 +1559,7 @@ int yh_q_step_fused(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_overlap
     db->pend_excl_out = db->pend_red >= 0 ? db->pend_red_out[1] : nullptr;
     db->pend_red = c_new;
     if (d_sample) {
-        db->pend_red_parity = (int)(db->pipe_k & 1);
+        db->pend_red_parity = (int)((db->pipe_k & 1) | (R << 1));
         db->pend_red_out[0] = d_overlap;
         db->pend_red_out[1] = d_excl;
         db->pend_red_out[2] = d_match;
