@@ -302,6 +302,8 @@ int yh_run_device_join(yh_db* db);
  *   yh_gather / yh_gather_device                             | yes (no step state is read or written) | yes
  *   yh_gather_batch / yh_gather_batch_device                 | yes (no step state is read or written) | yes
  *   yh_lca / yh_lca_device, yh_db_set_taxonomy               | yes (no step state is read or written) | yes
+ *   yh_lca_batch / yh_lca_batch_device,                      | yes (no step state is read or written) | yes
+ *     yh_lca_rows_pack_device                                |                                       |
  *   yh_db_set_stream                                         | yes (drains the old stream first)      | yes
  *   (*) the CURRENT context = the one named by the last yh_run_local*_device / yh_run_finish*_device call (0 at start).
  * Every query entry point first completes the pending stages of pipelined steps (yh_run_device_join) by itself.          */
@@ -665,6 +667,51 @@ int yh_db_get_taxonomy(yh_db* db, uint32_t* n_nodes, uint64_t* device_bytes);
 int yh_lca_device(yh_db* db, const uint64_t* d_sample, const uint32_t* d_abund /* NULL: all 1 */, uint64_t n_sample,
                   uint32_t* d_node /* [n_sample] or NULL */, uint64_t* d_counts /* [n_nodes][2] */);
 int yh_lca(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_t n_sample, uint32_t* node, uint64_t* counts);
+
+/* ---- the same for a BLOCK of samples under the taxonomy set, and its counts as rows (additive in ABI 8) ----------------------
+ * The single call is launch-bound for a real sample (14 us for 83 k hashes, much of it launch and ramp).  yh_lca_batch_device
+ * answers 1..YH_BATCH_MAX_SAMPLES samples in ONE clear and ONE lookup launch.  The block is laid out exactly as for
+ * yh_explain_batch_device: samples back to back, strictly ascending inside each sample, device offsets [n_samples + 1], and
+ * total_hashes (< 2^32) as the caller's copy of d_sample_offsets[n_samples] that only sizes launches (the offsets must ascend
+ * and stay inside d_samples, d_abund and d_node, and total_hashes must not be below the last offset: they are not checked).
+ * Contract: for every sample s,
+ *   d_node[off[s] .. off[s + 1])   and   d_counts[s][.][.]
+ * are bit-identical to what yh_lca_device returns for that sample alone under the taxonomy currently set.  All n_samples *
+ * n_nodes * 2 cells are cleared by the call: nothing of an earlier, larger block survives.  An empty database or total_hashes
+ * == 0: zero counts, and no node is written.  d_node and d_abund may be NULL (counts only; every abundance 1).
+ * How it runs: a workgroup takes a tile of YH_LCA_BATCH_TILE consecutive hashes of one sample, in yh_explain_batch_device's
+ * tile order; each hit is one dependent 4-byte read; a hit table in LDS keyed by node is flushed per tile with one 64-bit
+ * atomic per (tile, node, column), and a crowded table adds to global memory directly.  Integer adds only: the result does not
+ * depend on arrival order.  No host sync: the call is enqueued on the handle's stream.  It reads no step context, batch slot
+ * or work list (interleaving table above: yes / yes), completes pending pipelined stages first, and waits for a finish
+ * stream's rows.
+ * MEMORY: the dense counts are the caller's, 16 bytes per (sample, node) cell -- about 445 MB for 256 samples x 108 562 nodes,
+ * the size of the gather pass's working set.
+ * yh_lca_rows_pack_device turns such counts into rows: the non-zero cells (n_hashes != 0) in ascending (sample, node) order --
+ * a deterministic order, no atomic decides a position.  *d_n_rows (DEVICE) is the true number of non-zero cells even when it
+ * exceeds cap_rows; then exactly the first cap_rows rows of that order are written (yh_run_batch_rows_pack_device's
+ * convention).  Rows behind the count are not written; cap_rows == 0 writes nothing but still counts.  Three launches
+ * whatever n_samples is (count per chunk of cells, scan of the chunk counts, write), 8 bytes per 2 048 cells from the handle's
+ * buffer cache, no host sync.  n_nodes is that of the taxonomy currently set.
+ * YH_ERR_INVALID_ARG: n_samples == 0 or > YH_BATCH_MAX_SAMPLES, total_hashes >= 2^32.  YH_ERR_UNSUPPORTED exactly where
+ * yh_lca_device returns it.  yh_lca_batch is the synchronous host form (total = sample_offsets[n_samples]): it validates
+ * every sample's ordering (YH_ERR_UNSORTED), then uploads, runs and downloads; node [total] or NULL, counts
+ * [n_samples][n_nodes][2].
+ * Hash-range shards: as for yh_lca_device, nothing is built.                                                                  */
+#ifndef YH_LCA_BATCH_TILE
+#define YH_LCA_BATCH_TILE 1024 /* consecutive hashes of one sample a lookup workgroup takes */
+#endif
+typedef struct yh_lca_row {
+    uint32_t sample, node;
+    uint64_t n_hashes, w_hashes; /* counts[sample][node][0] and [1] */
+} yh_lca_row;
+int yh_lca_batch_device(yh_db* db, const uint64_t* d_samples, const uint64_t* d_sample_offsets /* [n_samples + 1] */,
+                        const uint32_t* d_abund /* [total_hashes] or NULL: all 1 */, uint32_t n_samples, uint64_t total_hashes,
+                        uint32_t* d_node /* [total_hashes] or NULL */, uint64_t* d_counts /* [n_samples][n_nodes][2] */);
+int yh_lca_batch(yh_db* db, const uint64_t* samples, const uint64_t* sample_offsets, const uint32_t* abund, uint32_t n_samples,
+                 uint32_t* node, uint64_t* counts);
+int yh_lca_rows_pack_device(yh_db* db, const uint64_t* d_counts /* [n_samples][n_nodes][2] */, uint32_t n_samples,
+                            yh_lca_row* d_rows, uint64_t cap_rows, uint64_t* d_n_rows /* DEVICE */);
 
 /* ---- the subset words of a block in compact form (ABI 5) ----------------------------------------------------------------
  * Between the two halves of a batched hash-range run every rank needs the OR of all ranks' subset words.  The dense row

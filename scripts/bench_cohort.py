@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """`yacht run` over a cohort (yacht_amd/cohort.py) end to end, on a synthetic database with real-shape samples.
 
-    python scripts/bench_cohort.py [--n-refs 85205] [--samples 1024] [--single 32] [--residual] [--abundance] [--gather --gather_top K] [--commit ID] [--out FILE]
+    python scripts/bench_cohort.py [--n-refs 85205] [--samples 1024] [--single 32] [--residual] [--abundance] [--gather --gather_top K] [--lineages [--lineages_rank RANK]] [--commit ID] [--out FILE]
 
 Prints one JSON line: samples/s of the cohort command with its phase split (yacht_amd/cohort.py main: check, db, table,
 device_setup, parse_wait, device_wait, the device time of uploads / batch counts + compact rows / presence kernel, d2h,
@@ -10,8 +10,11 @@ through the single-sample command in the same process (warm) for comparison.  --
 commands) with `yacht run --residual`: gpu_explain is then the phase of the residual's device work.  --abundance runs them with `yacht run --abundance`: gpu_abund is
 the device time of the blocks' depth passes (YACHT_COHORT_ABUND=loop in the environment: the per-sample loop).  --gather
 --gather_top K runs them with `yacht run --gather --gather_top K`: gpu_gather is the device time of the blocks' rankings
-(YACHT_COHORT_GATHER=loop in the environment: the host wall time of one host-form call per sample and coverage).  --commit is
-recorded."""
+(YACHT_COHORT_GATHER=loop in the environment: the host wall time of one host-form call per sample and coverage).  --lineages
+runs them with `yacht run --lineages FILE --lineages_rank RANK` over a synthetic lineage table (four consecutive organisms to
+a genus, four genera to a family, and so on up): gpu_lca is the device time of the blocks' yh_lca_batch_device and rows pack
+(YACHT_COHORT_LCA=loop in the environment: the HOST WALL time of one host-form yh_lca call per sample, not device time).
+--commit is recorded."""
 from __future__ import annotations
 
 import argparse
@@ -51,6 +54,17 @@ def make_db(tmp, n_refs, seed):
         json.dump({"manifest_file_path": os.path.join(tmp, "db_manifest.tsv"), "intermediate_files_dir": work, "scale": 1000,
                    "ksize": 31, "ani_thresh": 0.95}, f)
     return cfg, values, offsets
+
+
+def make_lineages(tmp, n_refs):
+    """A lineage table over make_db's organisms: a species each, four consecutive ones to a genus, four genera to a family, ..."""
+    path = os.path.join(tmp, "lineages.csv")
+    with open(path, "w") as f:
+        f.write("ident,superkingdom,phylum,class,order,family,genus,species\n")
+        for i in range(n_refs):
+            g = i // 4
+            f.write(f"organism {i},k{g // 4096:02d},p{g // 1024:03d},c{g // 256:04d},o{g // 64:05d},f{g // 16:05d},g{g:06d},g{g:06d}s{i:06d}\n")
+    return path
 
 
 _REFS = None  # the references, for the sample workers (inherited by fork: this runs before anything touches the GPU)
@@ -135,6 +149,8 @@ def main():
     ap.add_argument("--abundance", action="store_true")
     ap.add_argument("--gather", action="store_true")
     ap.add_argument("--gather_top", type=int, default=None)
+    ap.add_argument("--lineages", action="store_true")
+    ap.add_argument("--lineages_rank", default="genus")
     ap.add_argument("--commit", default="")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -149,7 +165,9 @@ def main():
     os.makedirs(out)
     args = SimpleNamespace(json=cfg, sample_file=paths, significance=0.99, num_threads=a.threads, keep_raw=False, show_all=False,
                            min_coverage_list=COVS, outdir=out, residual=a.residual, residual_coverage=None,
-                           abundance=a.abundance, gather=a.gather, gather_top=a.gather_top, gather_min_hits=1, gather_coverage=None)
+                           abundance=a.abundance, gather=a.gather, gather_top=a.gather_top, gather_min_hits=1, gather_coverage=None,
+                           lineages=make_lineages(tmp, a.n_refs) if a.lineages else None,
+                           lineages_rank=a.lineages_rank if a.lineages else None)
     t0 = time.perf_counter()
     phases = cohort.main(args, paths)
     wall = time.perf_counter() - t0
@@ -177,6 +195,9 @@ def main():
         "gather": bool(a.gather),
         "gather_top": a.gather_top,
         "cohort_gather": os.environ.get("YACHT_COHORT_GATHER", ""),
+        "lineages": bool(a.lineages),
+        "lineages_rank": a.lineages_rank if a.lineages else None,
+        "cohort_lca": os.environ.get("YACHT_COHORT_LCA", ""),
         "setup_s": round(setup_s, 1),
         "bottleneck": None,
         "cohort": {"samples": a.samples, "wall_s": round(wall, 2), "samples_per_s": round(a.samples / wall, 2),
@@ -189,7 +210,7 @@ def main():
                            "first_s": round(single_s[0], 3) if single_s else None,
                            "samples_per_s_warm": round(len(single_s[1:]) / sum(single_s[1:]), 2) if len(single_s) > 1 else None},
     }
-    host_phases = {k: v for k, v in phases.items() if k not in ("total", "dense_fallback_blocks") and not k.startswith("gpu_")}
+    host_phases = {k: v for k, v in phases.items() if k not in ("total", "dense_fallback_blocks", "lca_repacked_blocks") and not k.startswith("gpu_")}
     res["bottleneck"] = max(host_phases, key=host_phases.get)
     if single_s:
         res["cohort_speedup_vs_single_warm"] = round(res["cohort"]["samples_per_s"] / max(res["single_command"]["samples_per_s_warm"] or 1e-9, 1e-9), 2)

@@ -18,7 +18,15 @@ Before anything is timed, the device's nodes and counts of the first sample of e
 nothing with the kernels: all (hash, reference) pairs sorted by torch, the holders of a sample hash found by searchsorted, and
 the LCA taken as the longest common prefix of the holders' ancestor PATHS (a table of every node's ancestor at every depth;
 per depth a segment minimum and maximum) -- no depth lifting.  Prints one JSON line and writes it to --out (default
-profiles/lca/bench_lca.json)."""
+profiles/lca/bench_lca.json).
+
+    python scripts/bench_lca.py --batch [--batch-iters 10] [--batch-warmup 3] [--rounds 3] [--out FILE]
+
+The batched leg alone (default --out profiles/lca/bench_lca_batch.json), on the same database and taxonomy: blocks of 256
+real-shape 83 k-hash samples and of 32 samples of 10^6 hashes, resident on the device with their abundances.  Timed, alternating
+inside each round: (a) one yh_lca_batch_device plus yh_lca_rows_pack_device, (b) a loop of yh_lca_device over the block's
+samples, (c) the batched call without the pack -- HIP events, us per sample, the median of the rounds with their spread.  Before
+anything is timed the block's dense counts must equal the loop's and the rows torch.nonzero of them, in order."""
 from __future__ import annotations
 
 import argparse
@@ -136,17 +144,127 @@ def timed_set_taxonomy(db, tree):
     return wall, (float(m.group(2)) if m else None)
 
 
+def batch_leg(args) -> dict:
+    """(a) one yh_lca_batch_device plus yh_lca_rows_pack_device against (b) a loop of yh_lca_device over the same resident
+    block, us per sample; the batched call alone is recorded beside them.  Equality with the loop -- every dense count, and
+    the rows against torch.nonzero of them -- is checked before anything is timed."""
+    import torch
+
+    dev = torch.device("cuda:0")
+    N = args.n_refs
+    values, offsets, _ = synth.config3_device(seed=1002, n_refs=N, n_sample=1000, device="cuda:0")
+    torch.cuda.synchronize()
+    plan = synth.global_db_plan(1002, N)
+    assert np.array_equal(plan["offsets"], offsets.cpu().numpy())
+    tree = taxonomy.build_tree([f"r{j}" for j in range(N)], synthetic_lineages(plan["parent"]))
+    db = RefDB.from_device(values.data_ptr(), offsets.data_ptr(), N)
+    stream = torch.cuda.Stream()
+    db.set_stream(stream.cuda_stream)
+    db.set_taxonomy(*tree[:3])
+    n_nodes = db.taxonomy_info()["n_nodes"]
+    g = torch.Generator(device=dev)
+    g.manual_seed(7)
+    result = {"bench": "lca_batch", "commit": args.commit, "n_refs": N, "n_hashes_db": int(values.numel()), "n_nodes": n_nodes,
+              "iters": args.batch_iters, "warmup": args.batch_warmup, "rounds": args.rounds, "tile": _lib.YH_LCA_BATCH_TILE,
+              "counts_bytes_per_sample": 16 * n_nodes, "shapes": {}}
+    for name, shape, n_sample, b in (("real_shape_83k_x256", "real", 83_000, 256), ("1e6_hash_x32", "present", 1_000_000, 32)):
+        samples = [synth.sample_device(values, offsets, seed=2900 + i, n_sample=n_sample, shape=shape) for i in range(b)]
+        offs = np.zeros(b + 1, dtype=np.int64)
+        offs[1:] = np.cumsum([int(s.numel()) for s in samples])
+        total = int(offs[-1])
+        d_samples = torch.cat(samples)
+        del samples
+        d_offs = torch.from_numpy(offs).to(dev)
+        d_abund = torch.randint(1, 1001, (total,), generator=g, device=dev, dtype=torch.int32)
+        counts = [torch.zeros((b, n_nodes, 2), dtype=torch.int64, device=dev) for _ in range(2)]
+        cap = b * 32768  # (a real-shape sample meets ~21 000 nodes, a 10^6-hash one ~200: fewer than that, checked below)
+        rows = torch.zeros((cap, 3), dtype=torch.int64, device=dev)
+        n_rows = torch.zeros(1, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()
+
+        def batched_alone():
+            db.lca_batch_device(d_samples.data_ptr(), d_offs.data_ptr(), d_abund.data_ptr(), b, total, 0, counts[0].data_ptr())
+
+        def batched():
+            batched_alone()
+            db.lca_rows_pack_device(counts[0].data_ptr(), b, rows.data_ptr(), cap, n_rows.data_ptr())
+
+        def looped():
+            for s in range(b):
+                o = int(offs[s])
+                db.lca_device(d_samples.data_ptr() + 8 * o, d_abund.data_ptr() + 4 * o, int(offs[s + 1]) - o, 0, counts[1][s].data_ptr())
+
+        batched()
+        looped()
+        db.synchronize()
+        assert torch.equal(counts[0], counts[1]) and int(counts[0][:, :, 0].sum(dim=1).min()) > 0, "the block differs from the loop"
+        k = int(n_rows[0])
+        at = torch.nonzero(counts[1][:, :, 0])  # row-major: ascending (sample, node)
+        assert k == int(at.shape[0]) <= cap, "the row count differs from the loop's non-zero cells"
+        view = rows[:k].cpu().numpy().reshape(-1).view(np.dtype([("sample", np.uint32), ("node", np.uint32), ("n", np.uint64), ("w", np.uint64)]))
+        picked = counts[1][at[:, 0], at[:, 1]].cpu().numpy()
+        at = at.cpu().numpy()
+        assert np.array_equal(view["sample"], at[:, 0]) and np.array_equal(view["node"], at[:, 1]), "the rows' order differs"
+        assert np.array_equal(view["n"].astype(np.int64), picked[:, 0]) and np.array_equal(view["w"].astype(np.int64), picked[:, 1])
+        calls = (("batched_us_per_sample", batched), ("looped_us_per_sample", looped), ("batched_without_pack_us_per_sample", batched_alone))
+        times = {k_: [] for k_, _ in calls}
+        with torch.cuda.stream(stream):
+            for _k, fn in calls:
+                for _ in range(args.batch_warmup):
+                    fn()
+            db.synchronize()
+            for _ in range(args.rounds):
+                for k_, fn in calls:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(stream)
+                    for _i in range(args.batch_iters):
+                        fn()
+                    e1.record(stream)
+                    e1.synchronize()
+                    times[k_].append(e0.elapsed_time(e1) * 1e3 / args.batch_iters / b)
+        out = {"samples": b, "total_hashes": total, "hashes_in_database": int(counts[0][:, :, 0].sum()), "rows": k,
+               "rows_per_sample_mean": round(k / b, 1), "counts_bytes": 16 * b * n_nodes,
+               "equal": "every dense count equals the loop's; the rows equal torch.nonzero of them in (sample, node) order"}
+        for k_, v in times.items():
+            out[k_] = round(float(np.median(v)), 2)
+            out[k_.replace("_us_per_sample", "_rounds_us_per_sample")] = [round(x, 2) for x in v]
+            out[k_.replace("_us_per_sample", "_spread_us_per_sample")] = round(max(v) - min(v), 2)
+        spread = max(out["batched_spread_us_per_sample"], out["looped_spread_us_per_sample"])
+        out["batched_over_looped"] = round(out["batched_us_per_sample"] / out["looped_us_per_sample"], 3)
+        # the expectation: batched plus pack no longer than the loop, judged against the rounds' spread
+        out["batched_not_slower"] = bool(out["batched_us_per_sample"] <= out["looped_us_per_sample"] + spread)
+        result["shapes"][name] = out
+        del d_samples, d_abund, counts, rows
+        torch.cuda.empty_cache()
+    db.close()
+    return result
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", action="store_true", help="the batched leg alone (yh_lca_batch_device + rows pack against a loop of yh_lca_device)")
+    ap.add_argument("--batch-iters", type=int, default=10)
+    ap.add_argument("--batch-warmup", type=int, default=3)
+    ap.add_argument("--commit", default="", help="recorded in the batched leg's output")
     ap.add_argument("--n-refs", type=int, default=85_205)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "lca", "bench_lca.json"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "lca",
+                                "bench_lca_batch.json" if args.batch else "bench_lca.json")
     import torch
 
     assert _lib.device_count() >= 1, "bench_lca.py needs an MI355X"
+    if args.batch:
+        line = json.dumps(batch_leg(args))
+        print(line)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+        return
     dev = torch.device("cuda:0")
     N = args.n_refs
     values, offsets, _ = synth.config3_device(seed=1002, n_refs=N, n_sample=1000, device="cuda:0")

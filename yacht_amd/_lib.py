@@ -38,6 +38,7 @@ YH_GATHER_BATCH_MAX_ROWS = 4096  # cap_rows of yh_gather_batch: its rounds are e
 YH_GATHER_NOBODY = 0xFFFFFFFF  # an owner entry: no reference took the hash
 YH_LCA_MAX_DEPTH = 16  # deepest node of a taxonomy (yh_db_set_taxonomy)
 YH_LCA_NONE = 0xFFFFFFFF  # a node entry: no reference holds the hash
+YH_LCA_BATCH_TILE = 1024
 YH_LOOKUP_AUTO, YH_LOOKUP_STREAM, YH_LOOKUP_INDEXED = 0, 1, 2
 
 _ERR_NAMES = {
@@ -176,6 +177,9 @@ SIGNATURES = {
     "yh_db_get_taxonomy": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "yh_lca_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp]),
     "yh_lca": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp]),
+    "yh_lca_batch_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp]),
+    "yh_lca_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp]),
+    "yh_lca_rows_pack_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp]),
     "yh_host_alloc": (C.c_int, [C.POINTER(_vp), C.c_uint64]),
     "yh_host_free": (C.c_int, [_vp]),
     "yh_db_nshared_device": (C.c_int, [_vp, _vp]),

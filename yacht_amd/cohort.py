@@ -11,6 +11,9 @@ j + 1, and a pool of --num_threads processes writes the tables.
 With --gather --gather_top K the block's ranking follows on the device (yh_explain_members_rows_device, then one
 yh_gather_batch_device per gather coverage): results/<stem>/gather_profile.tsv and results/cohort_gather.tsv.
 
+With --lineages --lineages_rank RANK the tree is built and set once, and per block one yh_lca_batch_device and one
+yh_lca_rows_pack_device follow: results/<stem>/lca_summary.tsv and results/cohort_lca.tsv, cut at RANK (taxonomy.rank_rows).
+
 Output: results/<stem>/ per sample with overlap (what a single-sample run of that file writes into results/),
 results/cohort_samples.tsv and results/cohort_presence.tsv.  Every input is checked before any device work; the
 per-sample intermediate files of the single path (multisearch CSV, list files) are not written.  Every sample is parsed
@@ -41,6 +44,9 @@ from .utils import logger
 BLOCK = _lib.YH_BATCH_MAX_SAMPLES  # samples per yh_run_batch_device
 MAX_COVS = _lib.YH_PRESENCE_MAX_COVS  # coverages per yh_presence_rows_device (more coverages take more launches)
 MAX_SETS = 7  # call sets per explain pass: bits 0..6 of a member byte (residual.MAX_SETS)
+# rows of a block's lineage counts the row buffer starts with at most (24 bytes each; a real-shape sample meets ~21 000 nodes);
+# it grows after a block that exceeded it
+LCA_ROWS_CAP = 1 << 23
 SAMPLE_COLUMNS = ["stem", "path", "n_hashes", "mean_abundance", "n_overlapping", "status"]
 PRESENCE_COLUMNS = ["sample", "min_coverage", "organism_name", "num_matches", "acceptance_threshold_with_coverage", "p_vals"]
 PRESENCE_ABUNDANCE_COLUMNS = ["abund_median_exclusive", "relative_abundance"]  # behind them with --abundance
@@ -98,6 +104,12 @@ def check_inputs(args, files: List[str]) -> dict:
         from . import gather
 
         gather.gather_options(args, len(files))
+    lineages = lineages_rank = None
+    if getattr(args, "lineages", None) is not None or getattr(args, "lineages_rank", None) is not None:
+        from . import taxonomy
+
+        lineages = taxonomy.lineages_option(args, len(files))
+        lineages_rank = taxonomy.lineages_rank(args)
     json_file_path = str(Path(args.json).absolute())
     paths = [str(Path(f).absolute()) for f in files]
     outdir = str(Path(args.outdir).absolute())
@@ -134,11 +146,20 @@ def check_inputs(args, files: List[str]) -> dict:
 
             raise ValueError(abundance.MSG_NO_ABUNDANCE.format(p))
         meta.append(m)
-    return dict(config=config, paths=paths, outdir=outdir, meta=meta)
+    return dict(config=config, paths=paths, outdir=outdir, meta=meta, lineages=lineages, lineages_rank=lineages_rank)
+
+
+_LCA_TREE = None  # (parent, leaf, node_lineages) of --lineages in a process of the write pool: sent once, not with every sample
+
+
+def _init_writer(tree) -> None:
+    global _LCA_TREE
+    _LCA_TREE = tree
 
 
 def _write_one(folder: str, results, covs, has_raw: bool, keep_raw: bool, show_all: bool, profile: bool = False, explained=None,
-               ranked=None) -> None:
+               ranked=None, lineage=None):
+    """One sample's files.  Returns its rows of cohort_lca.tsv (taxonomy.rank_rows) with --lineages, else None."""
     os.makedirs(folder, exist_ok=True)
     ry.write_sample_results(results, covs, has_raw, folder, keep_raw, show_all)
     if profile:
@@ -154,6 +175,17 @@ def _write_one(folder: str, results, covs, has_raw: bool, keep_raw: bool, show_a
         from . import gather
 
         gather.write_frame(folder, ranked)
+    if lineage is not None:  # the sample's non-zero lineage counts (node, n_hashes, w_hashes), its size and abundance, call sets, rank
+        from . import taxonomy
+
+        nodes, n_h, w_h, n_hashes, abund_total, call_sets, rank = lineage
+        parent, leaf, node_lineages = _LCA_TREE
+        counts = np.zeros((len(parent), 2), dtype=np.uint64)
+        counts[nodes, 0], counts[nodes, 1] = n_h, w_h
+        taxonomy.write_summary(folder, taxonomy.summary_frame(parent, leaf, node_lineages, counts, n_hashes, abund_total,
+                                                              covs if has_raw else covs[1:], call_sets))
+        return taxonomy.rank_rows(parent, leaf, node_lineages, counts, rank, n_hashes, abund_total)
+    return None
 
 
 class _Device:
@@ -161,14 +193,16 @@ class _Device:
 
     def __init__(self, db, covs, ksize: int, ani_thresh: float, thr_table: np.ndarray, cap: int = 0, abund_samples: int = 0,
                  residual_sets: int = 0, gather_sets=(), gather_min_hits: int = 1, gather_top: int = 0, n_user: int = 0,
-                 max_samples: int = BLOCK):
+                 max_samples: int = BLOCK, lca_nodes: int = 0, lca_cap: int = 0):
         """cap: compact rows a block may have before it takes the dense rows (0: BLOCK * N, at most 2^20; grows after a
         block that exceeded it).  abund_samples (--abundance): samples of the largest block; 0 = no abundance pass.
         residual_sets (--residual): the number of user coverages, the LAST residual_sets entries of covs, whose call sets
         the block's explain passes answer, seven per pass; 0 = no explain pass.  gather_sets (--gather): which of the n_user
         user coverages (indices into them; they are the LAST n_user entries of covs) the block's ranking is made for, with
         gather_min_hits and at most gather_top rows per sample and coverage, for blocks of up to max_samples; empty = no
-        ranking."""
+        ranking.  lca_nodes (--lineages): the nodes of the taxonomy set on db, for blocks of up to max_samples; 0 = no
+        lineage pass.  lca_cap: rows of a block's lineage counts the row buffer starts with (0: LCA_ROWS_CAP, at most one
+        per cell; it grows after a block that exceeded it)."""
         import torch
 
         self.torch = torch
@@ -214,6 +248,25 @@ class _Device:
             self.x_flags = None  # [passes][the block's hashes], made per block
             self.d_x_abund = None
             self.ev_explain = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        self.lca_nodes = int(lca_nodes)
+        if self.lca_nodes > 0:  # per block: dense counts [samples][nodes][2] (16 bytes a cell), their non-zero cells as rows
+            bmax = max(1, min(BLOCK, int(max_samples)))
+            self.l_counts = torch.zeros((bmax, self.lca_nodes, 2), dtype=torch.int64, device=self.dev)
+            self.l_n = torch.zeros(1, dtype=torch.int64, device=self.dev)
+            self.l_n_host = torch.zeros(1, dtype=torch.int64).pin_memory()
+            self._lca_alloc(int(lca_cap) if lca_cap > 0 else min(bmax * self.lca_nodes, LCA_ROWS_CAP))
+            self.ev_lca = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+
+    def _lca_alloc(self, cap: int) -> None:
+        self.l_cap = int(cap)
+        self.l_rows = self.torch.zeros((self.l_cap, 3), dtype=self.torch.int64, device=self.dev)  # (engine.LCA_ROW_DTYPE: 24 bytes)
+
+    def lca_pass(self, b: int, total: int) -> None:
+        """The block's lineage counts: one yh_lca_batch_device over the uploaded block, then their non-zero cells as rows
+        (yh_lca_rows_pack_device) and the row count on its way to the host.  No host sync."""
+        d_abund = self.d_x_abund.data_ptr() if self.d_x_abund is not None else 0
+        self.db.lca_batch_device(self.d_samples.data_ptr(), self.d_offs.data_ptr(), d_abund, b, total, 0, self.l_counts.data_ptr())
+        self.db.lca_rows_pack_device(self.l_counts.data_ptr(), b, self.l_rows.data_ptr(), self.l_cap, self.l_n.data_ptr())
 
     def _alloc(self, cap: int) -> None:
         t = self.torch
@@ -351,6 +404,12 @@ class _Device:
             self._upload_sketch_abundances(mins, abunds, explain_abunds, total)
             self.gather_pass(self.rows, self.n_rows[1].data_ptr(), self.cap, self.out, b, total)
             self.ev_gather[1].record()
+        if self.lca_nodes > 0:
+            self.ev_lca[0].record()  # (likewise)
+            self._upload_sketch_abundances(mins, abunds, explain_abunds, total)
+            self.lca_pass(b, total)
+            self.ev_lca[1].record()
+            self.l_n_host.copy_(self.l_n, non_blocking=True)
         self.n_rows_host.copy_(self.n_rows, non_blocking=True)
         return b
 
@@ -423,6 +482,25 @@ class _Device:
             g_rows = self.g_rows[:, :b, :longest].contiguous().cpu().numpy().reshape(len(self.gather_sets), b, longest * 3)
             got += ((g_rows.view(GATHER_ROW_DTYPE), g_n),)
         timer["d2h"] += time.perf_counter() - t0
+        if self.lca_nodes > 0:  # the block's lineage rows in (sample, node) order: always the LAST entry
+            from .engine import LCA_ROW_DTYPE
+
+            timer["gpu_lca"] += self.ev_lca[0].elapsed_time(self.ev_lca[1]) / 1e3
+            k = int(self.l_n_host[0])
+            if k > self.l_cap:  # more non-zero cells than the row buffer holds: the dense counts are still resident, pack them again
+                self._lca_alloc(int(k * 1.25) + 1)  # (the next blocks start with this capacity)
+                self.ev_lca[0].record()
+                self.db.lca_rows_pack_device(self.l_counts.data_ptr(), b, self.l_rows.data_ptr(), self.l_cap, self.l_n.data_ptr())
+                self.ev_lca[1].record()
+                t0 = time.perf_counter()
+                self.db.synchronize()
+                t.cuda.synchronize(self.dev)
+                timer["device_wait"] += time.perf_counter() - t0
+                timer["gpu_lca"] += self.ev_lca[0].elapsed_time(self.ev_lca[1]) / 1e3
+                timer["lca_repacked_blocks"] += 1
+            t0 = time.perf_counter()
+            got += (self.l_rows[:k].cpu().numpy().reshape(-1).view(LCA_ROW_DTYPE),)
+            timer["d2h"] += time.perf_counter() - t0
         return got
 
 
@@ -436,7 +514,9 @@ def main(args, files: List[str]) -> dict:
     the wall time of the host-form yh_explain calls of samples whose tables the host recomputed, or of every sample under
     YACHT_COHORT_EXPLAIN=host), gpu_gather (with --gather: device time of the block's member-row passes and batched rankings, plus
     the wall time of the host-form yh_gather calls of samples whose tables the host recomputed, or of every sample under
-    YACHT_COHORT_GATHER=loop), d2h, assemble, writes (what the write pool had left after the last block), cohort_files (the two
+    YACHT_COHORT_GATHER=loop), gpu_lca and lca_repacked_blocks (only with --lineages: device time of the block's
+    yh_lca_batch_device and rows pack -- under YACHT_COHORT_LCA=loop the HOST WALL time of every sample's host-form yh_lca call,
+    not device time -- and the blocks whose rows were packed a second time into a larger buffer), d2h, assemble, writes (what the write pool had left after the last block), cohort_files (the two
     cohort tables), total."""
     timer = {k: 0.0 for k in ("check", "db", "table", "device_setup", "parse_wait", "device_wait", "gpu_h2d", "gpu_counts",
                               "gpu_presence", "gpu_abund", "gpu_explain", "gpu_gather", "d2h", "assemble", "writes", "cohort_files", "dense_fallback_blocks", "total")}
@@ -487,28 +567,45 @@ def main(args, files: List[str]) -> dict:
     # YACHT_COHORT_GATHER=loop: every sample's ranking by its own host-form yh_gather calls (A/B checks); otherwise only
     # the samples whose tables the host recomputed below take them
     device_gather = gather_plan is not None and os.environ.get("YACHT_COHORT_GATHER") != "loop"
+    lineages, lca_rank = plan["lineages"], plan["lineages_rank"]
+    tree = None
+    if lineages is not None:  # the tree once from the manifest, set once on the resident database (references in manifest order)
+        from . import taxonomy
+
+        tree = taxonomy.build_tree(manifest["organism_name"], lineages)
+        db.set_taxonomy(*tree[:3])
+        lca_parts = []  # (stem, the sample's rows of cohort_lca.tsv or the future that returns them), in cohort order
+        timer["gpu_lca"] = timer["lca_repacked_blocks"] = 0.0
+    # YACHT_COHORT_LCA=loop: every sample's lineage counts by its own host-form yh_lca call (A/B checks; the same files)
+    device_lca = tree is not None and os.environ.get("YACHT_COHORT_LCA") != "loop"
     dev = _Device(db, covs, ksize, ani_thresh, t_thr, abund_samples=min(BLOCK, len(paths)) if want_abundance else 0,
                   residual_sets=len(user_covs) if device_explain else 0,
-                  **(dict(gather_sets=gather_idx, gather_min_hits=gather_plan[1], gather_top=gather_top, n_user=len(user_covs),
-                          max_samples=len(paths)) if device_gather else {}))
+                  **{**(dict(gather_sets=gather_idx, gather_min_hits=gather_plan[1], gather_top=gather_top, n_user=len(user_covs),
+                             max_samples=len(paths)) if device_gather else {}),
+                     **(dict(lca_nodes=len(tree[0]), max_samples=len(paths)) if device_lca else {})})
     timer["device_setup"] = time.perf_counter() - t0
 
     blocks = [list(range(i, min(i + BLOCK, len(paths)))) for i in range(0, len(paths), BLOCK)]
     summary, presence = [], []
     presence_columns = PRESENCE_COLUMNS + (PRESENCE_ABUNDANCE_COLUMNS if want_abundance else [])
     ctx = multiprocessing.get_context("spawn")  # (the parent holds the GPU: no fork)
-    pool = ProcessPoolExecutor(max_workers=max(1, int(args.num_threads)), mp_context=ctx)
+    pool = ProcessPoolExecutor(max_workers=max(1, int(args.num_threads)), mp_context=ctx,
+                               **(dict(initializer=_init_writer, initargs=((tree[0], tree[2], tree[3]),)) if tree is not None else {}))
     futures = []
     parse_pool = ThreadPoolExecutor(max(1, int(args.num_threads)))
+    want_sigs = want_residual or gather_plan is not None or tree is not None  # (the passes that take a sketch's own abundances)
 
     def parse(block):
-        if want_residual or gather_plan is not None:
+        if want_sigs:
             return [parse_pool.submit(_load_for_residual, paths[i], ksize, want_abundance) for i in block]
         return [parse_pool.submit(_load_mins_abund if want_abundance else _load_mins, paths[i], ksize) for i in block]
 
     def assemble(block, mins, got, abunds=None, sigs=None):
         rows, pv, pres, ncov = got[:4]
         t0 = time.perf_counter()
+        if device_lca:  # the block's lineage rows, ascending (sample, node): the last entry, taken off before the others are read
+            l_rows, got = got[-1], got[:-1]
+            l_bounds = np.searchsorted(l_rows["sample"], np.arange(len(block) + 1))
         if device_gather:  # the block's rows [gather coverages][samples][longest ranking] and their counts
             g_rows, g_n = got[-1]
         if device_explain:  # the block's flags [passes][hashes] and totals [passes][samples][8][2]
@@ -524,7 +621,11 @@ def main(args, files: List[str]) -> dict:
             stem = sample_stem(paths[i])
             summary.append([stem, paths[i], n_hashes, mean_abundance, int(sel.size), "ok" if sel.size else "no_overlap"]
                            + ([0.0, 0.0] if want_residual else []))  # (no overlap: nothing explained, and no device call)
+            if tree is not None:  # the sum of the sketch's own abundances, its size when it tracks none
+                lca_total = n_hashes if abunds[s] is None else int(np.asarray(abunds[s], dtype=np.uint64).sum(dtype=np.uint64))
             if not sel.size:
+                if tree is not None:  # (no reference holds a hash of it: its not_in_database row alone)
+                    lca_parts.append((stem, taxonomy.no_overlap_rows(n_hashes, lca_total)))
                 continue
             refs = rows[sel, 1].astype(np.int64)
             e = rows[sel, 3].astype(np.int64)
@@ -560,8 +661,8 @@ def main(args, files: List[str]) -> dict:
                 total = int(abunds[s].sum(dtype=np.uint64))
                 frames = [abundance.append_columns(f, *depth, total) for f in frames]
             frames = ry.trim_results(frames)
-            explained = ranked = None
-            if want_residual or gather_plan is not None:
+            explained = ranked = lineage = None
+            if want_sigs:
                 call_sets = [refs[df["in_sample_est"].to_numpy().astype(bool)] for df in (frames if has_raw else frames[1:])]
             if gather_plan is not None:
                 if device_gather and not recomputed:  # the device's present bytes ARE these call sets: the block's ranking
@@ -587,6 +688,17 @@ def main(args, files: List[str]) -> dict:
                 row = row[row["min_coverage"] == residual_cov].iloc[0]
                 summary[-1][-2:] = [float(row["f_hashes_explained"]), float(row["f_abund_explained"])]
                 explained = (sigs[s], call_sets, flags, totals, residual_cov)
+            if tree is not None:  # the sample's non-zero lineage counts; the write pool makes its table and its rows of the cohort's
+                if device_lca:
+                    mine = l_rows[l_bounds[s]:l_bounds[s + 1]]
+                    at, n_h, w_h = mine["node"].astype(np.int64), mine["n_hashes"].copy(), mine["w_hashes"].copy()
+                else:
+                    t1 = time.perf_counter()
+                    dense = db.lca(mins[s], abunds[s], want_nodes=False)[1]
+                    timer["gpu_lca"] += time.perf_counter() - t1  # (host wall time of the call, not device time)
+                    at = np.flatnonzero(dense[:, 0])
+                    n_h, w_h = dense[at, 0], dense[at, 1]
+                lineage = (at, n_h, w_h, n_hashes, lca_total, call_sets, lca_rank)
             for cov, df in zip(user_covs, frames if has_raw else frames[1:]):
                 hit = df[df["in_sample_est"] == True]  # noqa: E712
                 if len(hit):
@@ -598,7 +710,9 @@ def main(args, files: List[str]) -> dict:
                         part[c] = hit[c].to_numpy()
                     presence.append(pd.DataFrame(part, columns=presence_columns))
             futures.append(pool.submit(_write_one, os.path.join(results_folder, stem), frames, covs, has_raw, args.keep_raw,
-                                       args.show_all, want_abundance, explained, ranked))
+                                       args.show_all, want_abundance, explained, ranked, lineage))
+            if tree is not None:
+                lca_parts.append((stem, futures[-1]))
         timer["assemble"] += time.perf_counter() - t0
 
     try:
@@ -609,13 +723,13 @@ def main(args, files: List[str]) -> dict:
             t0 = time.perf_counter()
             mins = [f.result() for f in parsing]
             abunds = sigs = None
-            if want_residual or gather_plan is not None:  # (abundances where the sketch tracks them; --abundance has checked that every one does)
+            if want_sigs:  # (abundances where the sketch tracks them; --abundance has checked that every one does)
                 mins, abunds, sigs = [x[0] for x in mins], [x[1] for x in mins], [x[2] for x in mins]
             elif want_abundance:
                 mins, abunds = [x[0] for x in mins], [x[1] for x in mins]
             timer["parse_wait"] += time.perf_counter() - t0
             parsing = parse(blocks[j + 1]) if j + 1 < len(blocks) else []
-            b = dev.launch(mins, abunds if want_abundance else None, abunds if (device_explain or device_gather) and not want_abundance else None)
+            b = dev.launch(mins, abunds if want_abundance else None, abunds if (device_explain or device_gather or device_lca) and not want_abundance else None)
             if pending is not None:
                 assemble(*pending)  # (block j - 1 on the host while block j is on the device and block j + 1 is parsed)
             pending = (block, mins, dev.collect(b, timer), abunds, sigs)
@@ -636,6 +750,9 @@ def main(args, files: List[str]) -> dict:
     if gather_plan is not None:
         gather.cohort_frame([g[0] for g in gather_frames], [g[1] for g in gather_frames]).to_csv(
             os.path.join(results_folder, gather.COHORT_GATHER_NAME), sep="\t", index=False)
+    if tree is not None:
+        taxonomy.cohort_frame([p[0] for p in lca_parts], [p[1] if isinstance(p[1], list) else p[1].result() for p in lca_parts]).to_csv(
+            os.path.join(results_folder, taxonomy.COHORT_NAME), sep="\t", index=False)
     timer["cohort_files"] = time.perf_counter() - t0
     timer["total"] = time.perf_counter() - t_all
     logger.info(f"Saved results of {len(paths)} samples to {results_folder}.")

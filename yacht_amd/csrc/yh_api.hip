@@ -1460,6 +1460,88 @@ int yh_lca(yh_db* db, const uint64_t* sample, const uint32_t* abund, uint64_t n_
     return rc;
 }
 
+// ---- the same for a block of samples, and the block's counts as rows (yh_lca.hip) ----------------------------------
+static bool lca_batch_samples_ok(uint32_t n_samples) {
+    if (n_samples >= 1 && n_samples <= YH_BATCH_MAX_SAMPLES) return true;
+    yh_set_error("1..%d samples per batch", YH_BATCH_MAX_SAMPLES);
+    return false;
+}
+
+int yh_lca_batch_device(yh_db* db, const uint64_t* d_samples, const uint64_t* d_sample_offsets, const uint32_t* d_abund,
+                        uint32_t n_samples, uint64_t total_hashes, uint32_t* d_node, uint64_t* d_counts) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (!lca_batch_samples_ok(n_samples)) return YH_ERR_INVALID_ARG;
+    if (total_hashes >> 32) { yh_set_error("yh_lca_batch takes blocks below 2^32 hashes"); return YH_ERR_INVALID_ARG; }
+    YH_TRY(lca_supported(db));
+    if (!d_counts || !d_sample_offsets || (total_hashes && !d_samples)) { yh_set_error("null device pointer"); return YH_ERR_INVALID_ARG; }
+    YH_TRY(db_select(db));
+    YH_TRY(pipe_join(db));  // (no step context, batch slot or work list is read or written: nothing else to note)
+    fin_join(db);           // (a block whose rows the rows pack / unpack wrote on the finish stream)
+    return yh_q_lca_batch(db, yh_lca_taxonomy(db), (const u64*)d_samples, (const u64*)d_sample_offsets, d_abund, n_samples, total_hashes,
+                          d_node, (u64*)d_counts);
+}
+
+int yh_lca_rows_pack_device(yh_db* db, const uint64_t* d_counts, uint32_t n_samples, yh_lca_row* d_rows, uint64_t cap_rows,
+                            uint64_t* d_n_rows) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (!lca_batch_samples_ok(n_samples)) return YH_ERR_INVALID_ARG;
+    YH_TRY(lca_supported(db));
+    if (!d_counts || !d_n_rows || (cap_rows && !d_rows)) { yh_set_error("null device pointer"); return YH_ERR_INVALID_ARG; }
+    YH_TRY(db_select(db));
+    YH_TRY(pipe_join(db));
+    fin_join(db);
+    return yh_q_lca_rows_pack(db, yh_lca_taxonomy(db), (const u64*)d_counts, n_samples, d_rows, cap_rows, (u64*)d_n_rows);
+}
+
+int yh_lca_batch(yh_db* db, const uint64_t* samples, const uint64_t* sample_offsets, const uint32_t* abund, uint32_t n_samples,
+                 uint32_t* node, uint64_t* counts) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (!lca_batch_samples_ok(n_samples)) return YH_ERR_INVALID_ARG;
+    if (!sample_offsets || !counts) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+    const u64 total = sample_offsets[n_samples];
+    if (total >> 32) { yh_set_error("yh_lca_batch takes blocks below 2^32 hashes"); return YH_ERR_INVALID_ARG; }
+    if (sample_offsets[0] != 0 || (total && !samples)) { yh_set_error("bad sample arrays"); return YH_ERR_INVALID_ARG; }
+    for (uint32_t s = 0; s < n_samples; ++s) {
+        if (sample_offsets[s + 1] < sample_offsets[s] || sample_offsets[s + 1] > total ||
+            yh_q_check_sorted_host((const u64*)samples + sample_offsets[s], sample_offsets[s + 1] - sample_offsets[s]) != YH_OK) {
+            yh_set_error("sample %u is not strictly ascending", s);
+            return YH_ERR_UNSORTED;
+        }
+    }
+    YH_TRY(lca_supported(db));
+    YH_TRY(db_select(db));
+    const bool looks_up = total && db->n_refs && db->n_distinct;  // (otherwise: zero counts, no node written)
+    const u64 cells = 2 * (u64)n_samples * yh_lca_taxonomy(db).n_nodes;
+    u64 *d_s = nullptr, *d_o = nullptr;
+    u32* d_a = nullptr;
+    u64* d_out = nullptr;  // the counts, then the nodes
+    int rc = YH_OK;
+    do {
+        if (yh_tmalloc(db, (void**)&d_s, std::max<u64>(total, 2) * sizeof(u64)) != hipSuccess ||
+            yh_tmalloc(db, (void**)&d_o, (u64)(n_samples + 1) * sizeof(u64)) != hipSuccess ||
+            (abund && yh_tmalloc(db, (void**)&d_a, std::max<u64>(total, 4) * sizeof(u32)) != hipSuccess) ||
+            yh_tmalloc(db, (void**)&d_out, cells * sizeof(u64) + std::max<u64>(total, 4) * sizeof(u32)) != hipSuccess) {
+            yh_set_error("device allocation failed"); rc = YH_ERR_OOM; break;
+        }
+        if ((total && hipMemcpyAsync(d_s, samples, total * sizeof(u64), hipMemcpyHostToDevice, db->stream) != hipSuccess) ||
+            hipMemcpyAsync(d_o, sample_offsets, (u64)(n_samples + 1) * sizeof(u64), hipMemcpyHostToDevice, db->stream) != hipSuccess ||
+            (abund && total && hipMemcpyAsync(d_a, abund, total * sizeof(u32), hipMemcpyHostToDevice, db->stream) != hipSuccess)) {
+            yh_set_error("lca upload failed"); rc = YH_ERR_HIP; break;
+        }
+        u32* const d_node = node ? (u32*)(d_out + cells) : nullptr;
+        if ((rc = yh_lca_batch_device(db, (const uint64_t*)d_s, (const uint64_t*)d_o, abund ? d_a : nullptr, n_samples, total, d_node,
+                                      (uint64_t*)d_out)) != YH_OK) break;
+        const bool down_ok = hipMemcpyAsync(counts, d_out, cells * sizeof(u64), hipMemcpyDeviceToHost, db->stream) == hipSuccess &&
+                             (!node || !looks_up || hipMemcpyAsync(node, d_node, total * sizeof(u32), hipMemcpyDeviceToHost, db->stream) == hipSuccess);
+        if (!down_ok || hipStreamSynchronize(db->stream) != hipSuccess) {
+            yh_set_error("lca download failed: %s", hipGetErrorString(hipGetLastError()));
+            rc = YH_ERR_HIP;
+        }
+    } while (0);
+    yh_tfree(db, d_s); yh_tfree(db, d_o); yh_tfree(db, d_a); yh_tfree(db, d_out);
+    return rc;
+}
+
 // ---- the candidate references ranked by the sample hashes each adds (yh_gather.hip) ------------------------------
 int yh_gather_device(yh_db* db, const uint64_t* d_sample, const uint32_t* d_abund, uint64_t n_sample, const uint8_t* d_cand,
                      uint32_t min_hits, yh_gather_row* d_rows, uint64_t cap_rows, uint32_t* d_owner, uint64_t* n_rows, int* more) {

@@ -30,3 +30,14 @@ int yh_q_lca_index(yh_db* db, const u32* d_parent, const u8* d_depth, const u32*
 // enqueued on the handle's stream (include/yacht_hip.h: yh_lca_device).  d_abund may be null: every abundance is 1.  The
 // caller has checked the handle, its taxonomy and the pointers.
 int yh_q_lca(yh_db* db, const YhTaxonomy& t, const u64* d_sample, const u32* d_abund, u64 n_sample, u32* d_node, u64* d_counts);
+
+// The same for a block of n_samples samples laid out as for yh_explain_batch_device: node [total_hashes] (may be null) and
+// counts [n_samples][n_nodes][2], cleared here, in one clear and one lookup launch (include/yacht_hip.h: yh_lca_batch_device).
+// The caller has checked the handle, its taxonomy, the pointers, n_samples and total_hashes.
+int yh_q_lca_batch(yh_db* db, const YhTaxonomy& t, const u64* d_samples, const u64* d_soff, const u32* d_abund, u32 n_samples,
+                   u64 total_hashes, u32* d_node, u64* d_counts);
+
+// The non-zero cells of such counts as rows in (sample, node) order, the first cap_rows of them, and their true number in
+// *d_n_rows (device): three launches, no host sync (include/yacht_hip.h: yh_lca_rows_pack_device).
+int yh_q_lca_rows_pack(yh_db* db, const YhTaxonomy& t, const u64* d_counts, u32 n_samples, yh_lca_row* d_rows, u64 cap_rows,
+                       u64* d_n_rows);

@@ -107,6 +107,8 @@ def check_member(member, n_refs: int) -> np.ndarray:
 # one row of RefDB.gather (include/yacht_hip.h: yh_gather_row)
 GATHER_ROW_DTYPE = np.dtype([("ref", np.uint32), ("n_overlap", np.uint32), ("n_unique", np.uint32), ("reserved_", np.uint32),
                              ("w_unique", np.uint64)])
+# one row of RefDB.lca_rows_pack_device (include/yacht_hip.h: yh_lca_row)
+LCA_ROW_DTYPE = np.dtype([("sample", np.uint32), ("node", np.uint32), ("n_hashes", np.uint64), ("w_hashes", np.uint64)])
 
 
 def check_candidates(cand, n_refs: int) -> np.ndarray:
@@ -424,6 +426,44 @@ class RefDB:
         [n_nodes][2] counts out."""
         _lib.check(self._lib.yh_lca_device(self._h, C.c_void_p(d_sample), C.c_void_p(d_abund), n_sample, C.c_void_p(d_node),
                                            C.c_void_p(d_counts)))
+
+    def lca_batch(self, samples: Sequence[np.ndarray], abunds=None, want_nodes: bool = True):
+        """lca for a block of 1..256 samples in one lookup launch (yh_lca_batch).  abunds: None (all 1) or one entry per
+        sample, each an array of one abundance per hash or None (that sample's hashes count once).  Returns (nodes, counts):
+        nodes a list of uint32 arrays, one per sample (None with want_nodes=False), counts uint64 [len(samples), n_nodes, 2];
+        both equal lca's for each sample alone."""
+        b = len(samples)
+        if not 1 <= b <= _lib.YH_BATCH_MAX_SAMPLES:
+            raise ValueError(f"a block holds 1..{_lib.YH_BATCH_MAX_SAMPLES} samples, not {b}")
+        samples = [_as_u64(s) for s in samples]
+        cat_ab = None
+        if abunds is not None:
+            if len(abunds) != b:
+                raise ValueError(f"{len(abunds)} abundance arrays for {b} samples")
+            if any(a is not None for a in abunds):
+                parts = [np.ones(s.size, dtype=np.uint32) if a is None else check_abundances(s, a)[1] for s, a in zip(samples, abunds)]
+                cat_ab = np.ascontiguousarray(np.concatenate(parts), dtype=np.uint32)
+        values, offsets = pack_csr(samples)
+        nodes = np.full(values.size, _lib.YH_LCA_NONE, dtype=np.uint32) if want_nodes else None
+        counts = np.zeros((b, self.taxonomy_info()["n_nodes"], 2), dtype=np.uint64)
+        _lib.check(self._lib.yh_lca_batch(self._h, _ptr(values), _ptr(offsets), _ptr(cat_ab), b, _ptr(nodes), _ptr(counts)))
+        return ([nodes[int(offsets[s]):int(offsets[s + 1])] for s in range(b)] if want_nodes else None), counts
+
+    def lca_batch_device(self, d_samples: int, d_offsets: int, d_abund: int, n_samples: int, total_hashes: int, d_node: int,
+                         d_counts: int) -> None:
+        """yh_lca_batch_device: the block as for explain_batch_device and uint32 abundances (0: all 1) in, uint32
+        [total_hashes] nodes (0: none) and uint64 [n_samples][n_nodes][2] counts out.  Does not synchronize the host."""
+        _lib.check(self._lib.yh_lca_batch_device(self._h, C.c_void_p(d_samples), C.c_void_p(d_offsets), C.c_void_p(d_abund),
+                                                 n_samples, total_hashes, C.c_void_p(d_node), C.c_void_p(d_counts)))
+
+    def lca_rows_pack_device(self, d_counts: int, n_samples: int, d_rows: int, cap_rows: int, d_n_rows: int) -> None:
+        """yh_lca_rows_pack_device: the non-zero cells of uint64 [n_samples][n_nodes][2] counts as rows of LCA_ROW_DTYPE in
+        (sample, node) order, the first cap_rows of them, and their true number as one uint64 at d_n_rows (device).  Does not
+        synchronize the host."""
+        if int(cap_rows) < 0:
+            raise ValueError(f"cap_rows must be >= 0, not {cap_rows}")
+        _lib.check(self._lib.yh_lca_rows_pack_device(self._h, C.c_void_p(d_counts), n_samples, C.c_void_p(d_rows), int(cap_rows),
+                                                     C.c_void_p(d_n_rows)))
 
     def gather(self, sample, cand, abund=None, min_hits: int = 1, cap_rows: Optional[int] = None, want_owner: bool = False):
         """The candidates ranked by the sample hashes each adds (yh_gather): round after round the candidate holding the

@@ -78,7 +78,13 @@ ARGUMENTS = (
                              "or its first word).  Every sample hash is then classified by the lowest common ancestor of the "
                              "organisms that hold it: results/lca_summary.tsv, per taxon the sample hashes and abundance that "
                              "resolve exactly there and anywhere under it, and how many of its organisms were called present.  "
-                             "One sample file.")),
+                             "One sample file; a cohort with --lineages_rank: results/<stem>/lca_summary.tsv per sample and "
+                             "results/cohort_lca.tsv.")),
+    ("--lineages_rank", dict(type=str, default=None,
+                             help="The rank a cohort's lineage table is cut at (with --lineages): one of %s.  A cohort needs it: "
+                                  "results/cohort_lca.tsv then holds, per sample, the hashes outside the database, those that resolve "
+                                  "above the rank, and one row per taxon at the rank.  Ignored with one sample file."
+                                  % ", ".join(("superkingdom", "phylum", "class", "order", "family", "genus", "species", "strain")))),
 )
 
 # messages the reference raises with (callers and its tests match on them)
@@ -174,7 +180,7 @@ def main(args) -> None:
         gather_plan = gather.gather_options(args, len(files))  # (ValueError before anything is written or any device work)
         gather_cap = gather.gather_top(args, len(files))
     lineages = None
-    if getattr(args, "lineages", None) is not None:
+    if getattr(args, "lineages", None) is not None or getattr(args, "lineages_rank", None) is not None:
         from . import taxonomy
 
         lineages = taxonomy.lineages_option(args, len(files))  # (ValueError before anything is written or any device work)

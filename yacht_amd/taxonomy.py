@@ -4,6 +4,10 @@ The device answers, per sample hash, the lowest common ancestor of its holders i
 how many hashes resolve exactly there.  The taxonomy itself comes from a lineage table the user supplies -- the CSV that
 sourmash's `tax` and `lca` commands take -- and everything here is plain Python / numpy / pandas on it: reading the file,
 numbering the tree so that a parent comes before its children, the clade sums and the table.  No device, no library call.
+
+A cohort (`--lineages FILE --lineages_rank RANK` with two or more sample files; yacht_amd/cohort.py) gets the same table per
+sample and results/cohort_lca.tsv in long form, cut at RANK (rank_rows): over every taxon it would hold samples x taxa rows.
+Hash-range shards are not built for either form.
 """
 from __future__ import annotations
 
@@ -23,7 +27,14 @@ NOT_IN_DATABASE = "not_in_database"
 ROOT = "root"
 SUMMARY_COLUMNS = ["rank", "lineage", "num_hashes_direct", "num_hashes_clade", "f_hashes_clade", "abund_direct", "abund_clade",
                    "f_abund_clade", "n_refs_clade"]
-MSG_ONE_SAMPLE = "--lineages takes one sample file, not {0}: the cohort form is not built yet."
+COHORT_NAME = "cohort_lca.tsv"
+ABOVE_RANK = "above_rank"
+COHORT_COLUMNS = ["sample", "lineage", "num_hashes_clade", "f_hashes_clade", "abund_clade", "f_abund_clade", "n_refs_clade"]
+MSG_ONE_SAMPLE = ("--lineages takes one sample file, not {0}: a cohort's per-taxon table is cut at one rank (over every taxon it "
+                  "would hold samples x taxa rows).  Add --lineages_rank RANK (one of %s), run the samples one at a time, or drop "
+                  "--lineages." % ", ".join(RANKS))
+MSG_RANK_WITHOUT_LINEAGES = "--lineages_rank needs --lineages."
+MSG_BAD_RANK = "--lineages_rank {0} is not one of the ranks %s." % ", ".join(RANKS)
 MSG_NO_FILE = "--lineages file {0} does not exist."
 MSG_NO_IDENT = "--lineages file {0} has no `ident` column: its header is {1}."
 MSG_DUPLICATE = "--lineages file {0} lists {1} twice with different lineages."
@@ -144,12 +155,71 @@ def write_summary(results_folder: str, frame: pd.DataFrame) -> str:
     return path
 
 
+def rank_rows(parent, leaf, node_lineages, counts, rank: str, n_hashes: int, abund_total: int) -> List[list]:
+    """A sample's rows of cohort_lca.tsv behind its name, from RefDB.lca's counts [n_nodes, 2] cut at `rank`:
+    [lineage, num_hashes_clade, f_hashes_clade, abund_clade, f_abund_clade, n_refs_clade].  First `not_in_database`, the
+    hashes no reference holds; then `above_rank`, the hashes that resolve at a node shallower than the rank (its n_refs_clade:
+    the references hung that high); then one row per taxon AT the rank whose clade count is non-zero, ordered by lineage, with
+    the values of that taxon's row in lca_summary.tsv.  Every known hash resolves above the rank or under exactly one taxon
+    at it, so the rows add up to the sample's hashes and abundance."""
+    parent = np.asarray(parent, dtype=np.int64)
+    leaf = np.asarray(leaf, dtype=np.int64)
+    n_nodes = parent.size
+    at = RANKS.index(rank) + 1  # a taxon's depth is the length of its lineage
+    depth = np.array([len(p) for p in node_lineages], dtype=np.int64)
+    direct = np.asarray(counts, dtype=np.uint64).reshape(n_nodes, 2)
+    clade = clade_sums(parent, direct)
+    refs = clade_sums(parent, np.bincount(leaf, minlength=n_nodes))
+    n_hashes, abund_total = int(n_hashes), int(abund_total)
+
+    def frac(x, of):
+        return int(x) / of if of else 0.0
+
+    known_h, known_a = (int(clade[0, 0]), int(clade[0, 1])) if n_nodes else (0, 0)
+    above = depth < at
+    above_h, above_a = int(direct[above, 0].sum(dtype=np.uint64)), int(direct[above, 1].sum(dtype=np.uint64))
+    rows = [[NOT_IN_DATABASE, n_hashes - known_h, frac(n_hashes - known_h, n_hashes), abund_total - known_a,
+             frac(abund_total - known_a, abund_total), 0],
+            [ABOVE_RANK, above_h, frac(above_h, n_hashes), above_a, frac(above_a, abund_total), int(above[leaf].sum())]]
+    for v in sorted(np.flatnonzero((depth == at) & (clade[:, 0] != 0)).tolist(), key=lambda v: tuple(node_lineages[v])):
+        rows.append([";".join(node_lineages[v]), int(clade[v, 0]), frac(clade[v, 0], n_hashes), int(clade[v, 1]),
+                     frac(clade[v, 1], abund_total), int(refs[v])])
+    return rows
+
+
+def no_overlap_rows(n_hashes: int, abund_total: int) -> List[list]:
+    """rank_rows of a sample none of whose hashes the database holds: its `not_in_database` row alone."""
+    n_hashes, abund_total = int(n_hashes), int(abund_total)
+    return [[NOT_IN_DATABASE, n_hashes, 1.0 if n_hashes else 0.0, abund_total, 1.0 if abund_total else 0.0, 0]]
+
+
+def cohort_frame(stems: Sequence[str], rows: Sequence[List[list]]) -> pd.DataFrame:
+    """results/cohort_lca.tsv: the samples' rank_rows one after the other in the order given, behind a `sample` column."""
+    return pd.DataFrame([[stem] + r for stem, part in zip(stems, rows) for r in part], columns=COHORT_COLUMNS)
+
+
+def lineages_rank(args):
+    """RANK of `--lineages_rank RANK`, the rank a cohort's table is cut at; None without the option.  ValueError when it
+    comes without --lineages or names no rank."""
+    rank = getattr(args, "lineages_rank", None)
+    if rank is None:
+        return None
+    if getattr(args, "lineages", None) is None:
+        raise ValueError(MSG_RANK_WITHOUT_LINEAGES)
+    if str(rank) not in RANKS:
+        raise ValueError(MSG_BAD_RANK.format(rank))
+    return str(rank)
+
+
 def lineages_option(args, n_files: int):
-    """The lineage table of --lineages, read and checked, or None without the option.  ValueError for a bad or missing file
-    and for two or more sample files (the message names the option): before anything is written and before any device work."""
+    """The lineage table of --lineages, read and checked, or None without the option.  ValueError for a bad or missing file,
+    for --lineages_rank without --lineages or with an unknown rank, and for two or more sample files without
+    --lineages_rank (the message names the option): before anything is written and before any device work.  With one sample
+    file the rank is checked and otherwise ignored."""
+    rank = lineages_rank(args)
     path = getattr(args, "lineages", None)
     if path is None:
         return None
-    if n_files > 1:
+    if n_files > 1 and rank is None:
         raise ValueError(MSG_ONE_SAMPLE.format(n_files))
     return read_lineages(str(path))
