@@ -910,6 +910,42 @@ int yh_sketch_dna(const uint8_t* seq, uint64_t n_bytes, int ksize, uint64_t seed
 int yh_sketch_dna_device(const uint8_t* d_seq, uint64_t n_bytes, int ksize, uint64_t seed, uint64_t max_hash,
                          uint64_t cap, uint64_t* d_hashes_out, uint64_t* d_count, void* stream);
 
+/* ---- segmented sketching: many records in one buffer, one finished sketch per segment (additive to ABI 8) ----
+ * seg_off[n_seg + 1] are ascending byte offsets into seq, seg_off[0] = 0, seg_off[n_seg] = n_bytes; equal neighbours are
+ * an empty segment.  The window that starts at byte i belongs to the segment s with seg_off[s] <= i < seg_off[s + 1] and
+ * counts only if all its ksize bytes are A/C/G/T (either case) AND all lie inside segment s: segments may touch without a
+ * separator byte, and inside a segment any other byte (the '\n' between merged records) breaks windows as above.
+ * The sequence is hashed once; the (segment, hash) pairs are sorted and counted on the device.  The result is a CSR:
+ *   mins[]            uint64, strictly ascending inside each segment (the same hash in two segments stays in both)
+ *   abund[]           uint32, how many windows of the segment gave that hash
+ *   off[n_seg + 1]    the segments' extents in mins / abund
+ * mins and off are exactly what yh_db_create_device takes as d_values and d_offsets.  The same input gives the same bytes.
+ * Limits: n_bytes < 2^32 and n_seg < 2^32 per call (YH_ERR_INVALID_ARG beyond), ksize 1..255.
+ * (What the reference does here: `sourmash sketch dna --singleton` / `sketch fromfile`, one record or file after the
+ * other -- sketch_ref_genomes.py:25,61.)
+ *
+ * yh_sketch_segments_work_bytes   bytes of d_work the device form needs for cap_kept pairs: the pairs (twice), the sorts'
+ *                                 temporary storage and the scan; 0 when it cannot be told (no device: see yh_last_error)
+ * yh_sketch_segments_device       everything on device buffers, enqueued on `stream` without synchronizing, nothing
+ *                                 allocated.  d_totals[0] = kept hashes, d_totals[1] = distinct (segment, hash) pairs = entries
+ *                                 of mins.  Either may exceed its cap (cap_kept pairs, cap_mins entries): nothing behind a cap
+ *                                 is written, and d_off is still complete for the pairs that were stored, so the caller can
+ *                                 size a retry (with d_totals[0] > cap_kept the sketches are incomplete: retry with that many).
+ *                                 cap_mins = 0: d_mins / d_abund may be NULL.  The offsets are trusted: the segment search is
+ *                                 clamped to the table, so a bad table gives wrong sketches, never an access outside it.
+ * yh_sketch_segments              host buffers: seg_off is validated (YH_ERR_INVALID_ARG), the sequence is uploaded in pieces
+ *                                 under the hashing as yh_sketch_dna does, off_out[n_seg + 1] is always filled, *n_out = entries
+ *                                 of mins; two-call sizing: cap_mins = 0 only counts, YH_ERR_CAPACITY (with *n_out set) when
+ *                                 cap_mins is too small.                                                                  */
+uint64_t yh_sketch_segments_work_bytes(uint64_t cap_kept, uint64_t n_seg);
+int yh_sketch_segments_device(const uint8_t* d_seq, uint64_t n_bytes, const uint64_t* d_seg_off, uint64_t n_seg, int ksize,
+                              uint64_t seed, uint64_t max_hash, uint64_t cap_kept, void* d_work, uint64_t work_bytes,
+                              uint64_t cap_mins, uint64_t* d_mins, uint32_t* d_abund, uint64_t* d_off, uint64_t* d_totals,
+                              void* stream);
+int yh_sketch_segments(const uint8_t* seq, uint64_t n_bytes, const uint64_t* seg_off, uint64_t n_seg, int ksize, uint64_t seed,
+                       uint64_t max_hash, int device_id, uint64_t cap_mins, uint64_t* mins_out, uint32_t* abund_out,
+                       uint64_t* off_out, uint64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,10 +7,22 @@
 // algorithm by Austin Appleby) of its upper-case ASCII bytes, seed 42 -> kept iff <= max_hash.
 // One lane per window; the kept hashes (about 1/scaled of the windows) are appended unsorted, with
 // duplicates; the caller sorts and counts them (abundances).  ALU-bound, integer only.
+//
+// The SEGMENTED form (yh_sketch_segments*, further down): the buffer holds many records, seg_off[n_seg + 1] cuts it into
+// segments, and one hashing pass yields one finished sketch per segment in HBM.  The same kernels, instantiated with
+// SEG = true, emit (segment, hash) pairs: a window belongs to the segment its first byte lies in and counts only when all
+// its k bytes lie inside that segment (segments may touch without a separator byte).  The lookup runs only for KEPT hashes:
+// the window's position is parked beside the hash in the LDS list and resolved at the flush.  Then two radix sorts (by
+// hash, then stably by segment), a flag / scan / write sequence, and the result is a CSR: mins[] strictly ascending inside
+// each segment, abund[] their run lengths, off[n_seg + 1] -- mins and off are exactly what yh_db_create_device takes as
+// d_values and d_offsets.
 #include "yh_common.h"
 
 #include <algorithm>
 #include <mutex>
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 namespace {
 
@@ -38,17 +50,104 @@ __device__ __forceinline__ u32 base_code(u8 c) {
 }
 __device__ __forceinline__ u8 code_ascii(u32 code) { return (u8)((0x54474341u >> (8 * code)) & 0xffu); }
 
+// ---- segments (the SEG = true instantiations) ---------------------------------------------------------------------------------
+// off[n_seg + 1] ascending byte offsets, n_seg >= 1; out_seg[] receives the segment of every hash stored in out[]
+struct SegArgs {
+    const u64* off;
+    u32 n_seg;
+    u32* out_seg;
+};
+constexpr u32 SEG_NONE = 0xffffffffu;
+
+// the largest s in [lo, hi] with off[s] <= pos (lo when there is none): every read is inside off[lo .. hi], whatever the table holds
+__device__ __forceinline__ u32 seg_find(const u64* __restrict__ off, u64 pos, u32 lo, u32 hi) {
+    while (lo < hi) {
+        const u32 m = lo + (hi - lo + 1u) / 2u;
+        if (off[m] <= pos) lo = m; else hi = m - 1u;
+    }
+    return lo;
+}
+// the segment of the window that starts at pos (looked for in [lo, hi] <= n_seg - 1), SEG_NONE when its k bytes leave the segment
+__device__ __forceinline__ u32 seg_of_window(const SegArgs& sa, u64 pos, u32 k, u32 lo, u32 hi) {
+    const u32 s = seg_find(sa.off, pos, lo, hi);
+    return (sa.off[s] <= pos && pos + k <= sa.off[s + 1]) ? s : SEG_NONE;
+}
+// the segments a workgroup's windows [first, last] can start in -> lrange[0 .. 1] (two lanes of two waves; before a barrier)
+__device__ __forceinline__ void seg_range(const SegArgs& sa, u64 first, u64 last, u32* lrange) {
+    if (threadIdx.x == 0) lrange[0] = seg_find(sa.off, first, 0u, sa.n_seg - 1u);
+    if (threadIdx.x == 64) lrange[1] = seg_find(sa.off, last, 0u, sa.n_seg - 1u);
+}
+
+// A kept hash: into the workgroup's LDS list (SEG: with the position of its window, resolved at the flush), or, when the
+// list is full, straight out (SEG: resolved here -- only this path pays a search per hash, and only at scaled close to 1).
+template <bool SEG>
+__device__ __forceinline__ void sk_keep(u64 h1, u64 pos, u32 k, u64* lbuf, u32* lpos, u32* lfill, const u32* lrange, const SegArgs& sa,
+                                        u64 cap, u64* __restrict__ out, u64* __restrict__ out_count) {
+    const u32 slot = atomicAdd(lfill, 1u);
+    if (slot < (u32)SK_LCAP) {
+        lbuf[slot] = h1;
+        if constexpr (SEG) lpos[slot] = (u32)pos;
+    } else {  // scaled close to 1: more kept hashes than the LDS list holds
+        u32 s = 0;
+        if constexpr (SEG) {
+            s = seg_of_window(sa, pos, k, lrange[0], lrange[1]);
+            if (s == SEG_NONE) return;
+        }
+        const u64 g = atomicAdd((unsigned long long*)out_count, 1ull);
+        if (g < cap) {
+            out[g] = h1;
+            if constexpr (SEG) sa.out_seg[g] = s;
+        }
+    }
+}
+// The LDS list out, behind a barrier that follows the last sk_keep.  SEG: every entry's segment first (lanes in parallel,
+// a search over the few segments of this workgroup's span), windows that leave their segment dropped, the rest compacted.
+template <bool SEG, int THREADS>
+__device__ __forceinline__ void sk_flush(u32 k, u64* lbuf, u32* lpos, u32* lfill, u32* lkept, u64* gbase, const u32* lrange, const SegArgs& sa,
+                                         u64 cap, u64* __restrict__ out, u64* __restrict__ out_count) {
+    const u32 f = min(*lfill, (u32)SK_LCAP);
+    if (!f) return;
+    if constexpr (!SEG) {
+        if (threadIdx.x == 0) *gbase = atomicAdd((unsigned long long*)out_count, (unsigned long long)f);
+        __syncthreads();
+        for (u32 e = threadIdx.x; e < f; e += THREADS)
+            if (*gbase + e < cap) out[*gbase + e] = lbuf[e];
+    } else {
+        u32 mine = 0;
+        for (u32 e = threadIdx.x; e < f; e += THREADS) {
+            const u32 s = seg_of_window(sa, (u64)lpos[e], k, lrange[0], lrange[1]);
+            lpos[e] = s;
+            mine += (s != SEG_NONE) ? 1u : 0u;
+        }
+        const u32 base = mine ? atomicAdd(lkept, mine) : 0u;
+        __syncthreads();
+        if (threadIdx.x == 0) *gbase = *lkept ? atomicAdd((unsigned long long*)out_count, (unsigned long long)*lkept) : 0ull;
+        __syncthreads();
+        u64 g = *gbase + base;
+        for (u32 e = threadIdx.x; e < f; e += THREADS) {
+            const u32 s = lpos[e];
+            if (s == SEG_NONE) continue;
+            if (g < cap) { out[g] = lbuf[e]; sa.out_seg[g] = s; }
+            ++g;
+        }
+    }
+}
+
 // (win0: the first window of this launch -- a sequence that is still arriving is hashed piece by piece; n: bytes present)
+template <bool SEG>
 __global__ void __launch_bounds__(SK_THREADS) k_sketch_dna(const u8* __restrict__ seq, u64 n, u32 k, u64 seed,
                                                            u64 max_hash, u64 cap, u64* __restrict__ out,
-                                                           u64* __restrict__ out_count, u64 win0) {
+                                                           u64* __restrict__ out_count, u64 win0, const SegArgs sa) {
     __shared__ u64 lbuf[SK_LCAP];
-    __shared__ u32 lfill;
+    __shared__ u32 lpos[SEG ? SK_LCAP : 1];
+    __shared__ u32 lrange[2];
+    __shared__ u32 lfill, lkept;
     __shared__ u64 gbase;
-    if (threadIdx.x == 0) lfill = 0;
-    __syncthreads();
+    if (threadIdx.x == 0) { lfill = 0; lkept = 0; }
     const u64 n_win = n - k + 1;
     const u64 block_first = win0 + (u64)blockIdx.x * SK_THREADS * SK_ITEMS;
+    if constexpr (SEG) seg_range(sa, block_first, min(block_first + SK_THREADS * SK_ITEMS - 1, n - 1), lrange);
+    __syncthreads();
     for (int it = 0; it < SK_ITEMS; ++it) {
         const u64 i = block_first + (u64)it * SK_THREADS + threadIdx.x;
         if (i >= n_win) continue;
@@ -101,24 +200,10 @@ __global__ void __launch_bounds__(SK_THREADS) k_sketch_dna(const u8* __restrict_
         h1 += h2; h2 += h1;
         h1 = fmix64(h1); h2 = fmix64(h2);
         h1 += h2;
-        if (h1 <= max_hash) {
-            const u32 slot = atomicAdd(&lfill, 1u);
-            if (slot < (u32)SK_LCAP) {
-                lbuf[slot] = h1;
-            } else {  // scaled close to 1: more kept hashes than the LDS list holds
-                const u64 g = atomicAdd((unsigned long long*)out_count, 1ull);
-                if (g < cap) out[g] = h1;
-            }
-        }
+        if (h1 <= max_hash) sk_keep<SEG>(h1, i, k, lbuf, lpos, &lfill, lrange, sa, cap, out, out_count);
     }
     __syncthreads();
-    const u32 f = min(lfill, (u32)SK_LCAP);
-    if (f) {
-        if (threadIdx.x == 0) gbase = atomicAdd((unsigned long long*)out_count, (unsigned long long)f);
-        __syncthreads();
-        for (u32 e = threadIdx.x; e < f; e += SK_THREADS)
-            if (gbase + e < cap) out[gbase + e] = lbuf[e];
-    }
+    sk_flush<SEG, SK_THREADS>(k, lbuf, lpos, &lfill, &lkept, &gbase, lrange, sa, cap, out, out_count);
 }
 
 // ---- k <= 64: the k-mer as a 2-bit string in one 64- or 128-bit word ---------------------------------------------------------
@@ -166,19 +251,22 @@ __device__ __forceinline__ u32 top_bit_plus1(u128 x) {
 }
 
 // KW = 1: k <= 32, the k-mer in one 64-bit word; KW = 2: k <= 64, in a 128-bit one (the same code on a wider word)
-template <int KW>
+// (SEG: the segmented form -- kept hashes leave with their segment, see sk_keep / sk_flush; the per-window loop is the same)
+template <int KW, bool SEG>
 __global__ void __launch_bounds__(RL_THREADS) k_sketch_dna_roll(const u8* __restrict__ seq, u64 n, u32 k, u64 seed,
                                                                 u64 max_hash, u64 cap, u64* __restrict__ out,
-                                                                u64* __restrict__ out_count, u64 win0) {
+                                                                u64* __restrict__ out_count, u64 win0, const SegArgs sa) {
     typedef typename RollWord<KW>::type word;
     constexpr u32 BITS = 64u * KW;      // of a word = 32 KW bases
     constexpr int NW = 4 * KW;          // 8-byte ASCII words of a k-mer
     __shared__ u32 lcode[RL_UNITS];
     __shared__ u32 lbad[RL_UNITS];
     __shared__ u64 lbuf[SK_LCAP];
-    __shared__ u32 lfill;
+    __shared__ u32 lpos[SEG ? SK_LCAP : 1];
+    __shared__ u32 lrange[2];
+    __shared__ u32 lfill, lkept;
     __shared__ u64 gbase;
-    if (threadIdx.x == 0) lfill = 0;
+    if (threadIdx.x == 0) { lfill = 0; lkept = 0; }
     const u64 n_win = n - k + 1;
     const u64 B0 = win0 + (u64)blockIdx.x * RL_WIN;  // first base (= first window) of the workgroup
     for (u32 u = threadIdx.x; u < (u32)RL_UNITS; u += RL_THREADS) {
@@ -201,6 +289,7 @@ __global__ void __launch_bounds__(RL_THREADS) k_sketch_dna_roll(const u8* __rest
         lcode[u] = codes;
         lbad[u] = bad;
     }
+    if constexpr (SEG) seg_range(sa, B0, min(B0 + (u64)RL_WIN - 1, n - 1), lrange);
     __syncthreads();
     // the lane's 32 windows reach 32 + k - 1 <= 95 bases: units 2 l .. 2 l + 5 (six of sixteen bases; four when k <= 32)
     const u32 l2 = 2u * threadIdx.x;
@@ -265,41 +354,157 @@ __global__ void __launch_bounds__(RL_THREADS) k_sketch_dna_roll(const u8* __rest
         h1 += h2; h2 += h1;
         h1 = fmix64(h1); h2 = fmix64(h2);
         h1 += h2;
-        if (h1 <= max_hash) {
-            const u32 slot = atomicAdd(&lfill, 1u);
-            if (slot < (u32)SK_LCAP) {
-                lbuf[slot] = h1;
-            } else {  // scaled close to 1: more kept hashes than the LDS list holds
-                const u64 g = atomicAdd((unsigned long long*)out_count, 1ull);
-                if (g < cap) out[g] = h1;
-            }
-        }
+        if (h1 <= max_hash) sk_keep<SEG>(h1, w0 + t, k, lbuf, lpos, &lfill, lrange, sa, cap, out, out_count);
     }
     __syncthreads();
-    const u32 f = min(lfill, (u32)SK_LCAP);
-    if (f) {
-        if (threadIdx.x == 0) gbase = atomicAdd((unsigned long long*)out_count, (unsigned long long)f);
-        __syncthreads();
-        for (u32 e = threadIdx.x; e < f; e += RL_THREADS)
-            if (gbase + e < cap) out[gbase + e] = lbuf[e];
-    }
+    sk_flush<SEG, RL_THREADS>(k, lbuf, lpos, &lfill, &lkept, &gbase, lrange, sa, cap, out, out_count);
 }
 
 // The launch both entry points share: the windows [win0, win_end) of a sequence of which n_bytes are present (win0 a
 // multiple of SK_WIN_ALIGN); k <= 64 through the 2-bit kernel (YH_SKETCH_BYTES=1 behind the tuning gate: the first one).
 constexpr u64 SK_WIN_ALIGN = RL_WIN;  // (a multiple of both kernels' windows per workgroup)
 static_assert(RL_WIN % (SK_THREADS * SK_ITEMS) == 0, "one alignment for both kernels");
+// (sa: null = the plain form; else the segmented one, n_seg >= 1)
 static int launch_sketch(const u8* d_seq, u64 n_bytes, u32 k, u64 seed, u64 max_hash, u64 cap, u64* d_out, u64* d_cnt, hipStream_t st,
-                         u64 win0, u64 win_end) {
+                         u64 win0, u64 win_end, const SegArgs* sa = nullptr) {
     if (win_end <= win0) return YH_OK;
     static const bool bytes_only = yh_tune_flag("YH_SKETCH_BYTES");
     const bool roll = k <= 64 && !bytes_only && (reinterpret_cast<uintptr_t>(d_seq) & 15u) == 0;
     const u64 per_block = roll ? (u64)RL_WIN : (u64)SK_THREADS * SK_ITEMS;
     const u64 blocks = (win_end - win0 + per_block - 1) / per_block;
     if (blocks > 0x7fffffffull) { yh_set_error("sequence too long for one call"); return YH_ERR_INVALID_ARG; }
-    if (roll && k <= 32) k_sketch_dna_roll<1><<<(u32)blocks, RL_THREADS, 0, st>>>(d_seq, n_bytes, k, seed, max_hash, cap, d_out, d_cnt, win0);
-    else if (roll) k_sketch_dna_roll<2><<<(u32)blocks, RL_THREADS, 0, st>>>(d_seq, n_bytes, k, seed, max_hash, cap, d_out, d_cnt, win0);
-    else k_sketch_dna<<<(u32)blocks, SK_THREADS, 0, st>>>(d_seq, n_bytes, k, seed, max_hash, cap, d_out, d_cnt, win0);
+    const SegArgs none{nullptr, 0u, nullptr};
+    if (sa) {
+        if (roll && k <= 32) k_sketch_dna_roll<1, true><<<(u32)blocks, RL_THREADS, 0, st>>>(d_seq, n_bytes, k, seed, max_hash, cap, d_out, d_cnt, win0, *sa);
+        else if (roll) k_sketch_dna_roll<2, true><<<(u32)blocks, RL_THREADS, 0, st>>>(d_seq, n_bytes, k, seed, max_hash, cap, d_out, d_cnt, win0, *sa);
+        else k_sketch_dna<true><<<(u32)blocks, SK_THREADS, 0, st>>>(d_seq, n_bytes, k, seed, max_hash, cap, d_out, d_cnt, win0, *sa);
+    } else if (roll && k <= 32) k_sketch_dna_roll<1, false><<<(u32)blocks, RL_THREADS, 0, st>>>(d_seq, n_bytes, k, seed, max_hash, cap, d_out, d_cnt, win0, none);
+    else if (roll) k_sketch_dna_roll<2, false><<<(u32)blocks, RL_THREADS, 0, st>>>(d_seq, n_bytes, k, seed, max_hash, cap, d_out, d_cnt, win0, none);
+    else k_sketch_dna<false><<<(u32)blocks, SK_THREADS, 0, st>>>(d_seq, n_bytes, k, seed, max_hash, cap, d_out, d_cnt, win0, none);
+    YH_HIP(hipGetLastError());
+    return YH_OK;
+}
+
+// ---- (segment, hash) pairs -> the sketches as a CSR --------------------------------------------------------------------------
+// The pairs sit in cap slots; the first min(*n_kept, cap) are in (segment, hash) order after the two sorts, the slots nobody
+// wrote hold the segment n_seg and sort behind them.  k_seg_heads flags the first pair of every run of equal pairs (one word
+// per slot, and a zero behind the last); rocPRIM's exclusive scan of the flags is every slot's rank among the runs; k_seg_emit
+// writes a run's hash and length at its rank; k_seg_off finds every segment's first pair by binary search and stores that
+// pair's rank.  No atomic decides a position: the same input gives the same bytes.
+constexpr u32 SG_THREADS = 256;
+
+__global__ void __launch_bounds__(SG_THREADS) k_seg_heads(const u64* __restrict__ hash, const u32* __restrict__ seg, u64 cap,
+                                                          const u64* __restrict__ n_kept, u32* __restrict__ flag) {
+    const u64 i = (u64)blockIdx.x * SG_THREADS + threadIdx.x;
+    if (i > cap) return;
+    const u64 n = min(*n_kept, cap);
+    flag[i] = (i < n && (i == 0 || seg[i] != seg[i - 1] || hash[i] != hash[i - 1])) ? 1u : 0u;
+}
+
+__global__ void __launch_bounds__(SG_THREADS) k_seg_emit(const u64* __restrict__ hash, const u32* __restrict__ seg, u64 cap,
+                                                         const u64* __restrict__ n_kept, const u32* __restrict__ flag,
+                                                         const u32* __restrict__ rank, u64 cap_mins, u64* __restrict__ mins,
+                                                         u32* __restrict__ abund) {
+    const u64 i = (u64)blockIdx.x * SG_THREADS + threadIdx.x;
+    if (i >= cap || !flag[i]) return;
+    const u64 r = rank[i];
+    if (r >= cap_mins) return;
+    const u64 n = min(*n_kept, cap);
+    const u64 h = hash[i];
+    const u32 s = seg[i];
+    // the end of the run: the first pair behind i that differs (gallop, then bisect; most runs have one pair)
+    u64 lo = i, step = 1;     // (lo: known equal)
+    u64 hi = n;               // (hi: known different, or n)
+    while (lo + step < n) {
+        if (seg[lo + step] != s || hash[lo + step] != h) { hi = lo + step; break; }
+        lo += step;
+        step <<= 1;
+    }
+    while (lo + 1 < hi) {
+        const u64 m = lo + (hi - lo) / 2;
+        if (seg[m] == s && hash[m] == h) lo = m; else hi = m;
+    }
+    mins[r] = h;
+    abund[r] = (u32)(hi - i);
+}
+
+// one lane per s in [0, n_seg]: off[s] = rank of the first pair whose segment is >= s; the last one is the total, also -> *n_distinct
+__global__ void __launch_bounds__(SG_THREADS) k_seg_off(const u32* __restrict__ seg, u64 cap, const u64* __restrict__ n_kept,
+                                                        const u32* __restrict__ rank, u32 n_seg, u64* __restrict__ off,
+                                                        u64* __restrict__ n_distinct) {
+    const u64 s = (u64)blockIdx.x * SG_THREADS + threadIdx.x;
+    if (s > n_seg) return;
+    const u64 n = min(*n_kept, cap);
+    u64 lo = 0, hi = n;  // first i in [0, n] with seg[i] >= s
+    while (lo < hi) {
+        const u64 m = lo + (hi - lo) / 2;
+        if ((u64)seg[m] < s) lo = m + 1; else hi = m;
+    }
+    const u64 r = rank[lo];  // (rank has cap + 1 entries: rank[n] = all the runs)
+    off[s] = r;
+    if (s == n_seg) *n_distinct = r;
+}
+
+// the layout of the work buffer of yh_sketch_segments_device for cap pairs (offsets in bytes, every part 256-byte aligned)
+struct SegWork {
+    u64 hash_a, hash_b, seg_a, seg_b, flag, rank, tmp, tmp_bytes, total;
+};
+static int seg_work_layout(u64 cap, SegWork& w) {
+    size_t t1 = 0, t2 = 0, t3 = 0;
+    if (cap) {
+        YH_HIP(rocprim::radix_sort_pairs(nullptr, t1, (const u64*)nullptr, (u64*)nullptr, (const u32*)nullptr, (u32*)nullptr, (size_t)cap, 0u, 64u, (hipStream_t) nullptr));
+        YH_HIP(rocprim::radix_sort_pairs(nullptr, t2, (const u32*)nullptr, (u32*)nullptr, (const u64*)nullptr, (u64*)nullptr, (size_t)cap, 0u, 32u, (hipStream_t) nullptr));
+    }
+    YH_HIP(rocprim::exclusive_scan(nullptr, t3, (const u32*)nullptr, (u32*)nullptr, 0u, (size_t)cap + 1, rocprim::plus<u32>(), (hipStream_t) nullptr));
+    auto up = [](u64 x) { return (x + 255ull) & ~255ull; };
+    u64 at = 0;
+    w.hash_a = at; at += up(cap * sizeof(u64));
+    w.hash_b = at; at += up(cap * sizeof(u64));
+    w.seg_a = at; at += up(cap * sizeof(u32));
+    w.seg_b = at; at += up(cap * sizeof(u32));
+    w.flag = at; at += up((cap + 1) * sizeof(u32));
+    w.rank = at; at += up((cap + 1) * sizeof(u32));
+    w.tmp = at;
+    w.tmp_bytes = up(std::max<u64>(std::max<u64>(t1, t2), t3));
+    w.total = at + w.tmp_bytes + 256;  // (+ 256: the caller's buffer need not be aligned)
+    return YH_OK;
+}
+static u32 bits_of(u64 x) { u32 b = 1; while (b < 64 && (x >> b)) ++b; return b; }  // bits that hold x (at least one)
+
+static int seg_args_ok(u64 n_bytes, u64 n_seg, int ksize) {
+    if (ksize < 1 || ksize > 255) { yh_set_error("ksize must be in [1, 255]"); return YH_ERR_INVALID_ARG; }
+    if (n_bytes >= (1ull << 32)) { yh_set_error("a segmented call takes less than 2^32 bytes"); return YH_ERR_INVALID_ARG; }
+    if (n_seg >= (1ull << 32)) { yh_set_error("a segmented call takes less than 2^32 segments"); return YH_ERR_INVALID_ARG; }
+    return YH_OK;
+}
+
+// Everything behind the upload, on st: d_totals zeroed, the windows [win0, win_end) hashed into the pairs (win0 = 0 for a
+// resident sequence; the host form hashes the earlier windows itself, piece by piece, and passes hashed = true), sorted, cut.
+static int seg_finish(const u8* d_seq, u64 n_bytes, const u64* d_seg_off, u32 n_seg, u32 k, u64 seed, u64 max_hash, u64 cap_kept,
+                      u8* work, const SegWork& w, u64 cap_mins, u64* d_mins, u32* d_abund, u64* d_off, u64* d_totals, hipStream_t st,
+                      bool hashed) {
+    u64* hash_a = (u64*)(work + w.hash_a); u64* hash_b = (u64*)(work + w.hash_b);
+    u32* seg_a = (u32*)(work + w.seg_a); u32* seg_b = (u32*)(work + w.seg_b);
+    u32* flag = (u32*)(work + w.flag); u32* rank = (u32*)(work + w.rank);
+    if (!hashed) {
+        YH_HIP(hipMemsetAsync(d_totals, 0, 2 * sizeof(u64), st));
+        if (cap_kept) YH_HIP(hipMemsetD32Async((hipDeviceptr_t)seg_a, (int)n_seg, cap_kept, st));
+        if (n_bytes >= k) {
+            const SegArgs sa{d_seg_off, n_seg, seg_a};
+            YH_TRY(launch_sketch(d_seq, n_bytes, k, seed, max_hash, cap_kept, hash_a, d_totals, st, 0, n_bytes - k + 1, &sa));
+        }
+    }
+    if (cap_kept) {
+        size_t tb = w.tmp_bytes;
+        YH_HIP(rocprim::radix_sort_pairs(work + w.tmp, tb, (const u64*)hash_a, hash_b, (const u32*)seg_a, seg_b, (size_t)cap_kept, 0u, bits_of(max_hash), st));
+        tb = w.tmp_bytes;
+        YH_HIP(rocprim::radix_sort_pairs(work + w.tmp, tb, (const u32*)seg_b, seg_a, (const u64*)hash_b, hash_a, (size_t)cap_kept, 0u, bits_of(n_seg), st));  // stable: hashes stay ascending inside a segment
+    }
+    k_seg_heads<<<(u32)((cap_kept + 1 + SG_THREADS - 1) / SG_THREADS), SG_THREADS, 0, st>>>(hash_a, seg_a, cap_kept, d_totals, flag);
+    size_t tb = w.tmp_bytes;
+    YH_HIP(rocprim::exclusive_scan(work + w.tmp, tb, (const u32*)flag, rank, 0u, (size_t)cap_kept + 1, rocprim::plus<u32>(), st));
+    if (cap_kept && cap_mins) k_seg_emit<<<(u32)((cap_kept + SG_THREADS - 1) / SG_THREADS), SG_THREADS, 0, st>>>(hash_a, seg_a, cap_kept, d_totals, flag, rank, cap_mins, d_mins, d_abund);
+    k_seg_off<<<(u32)(((u64)n_seg + 1 + SG_THREADS - 1) / SG_THREADS), SG_THREADS, 0, st>>>(seg_a, cap_kept, d_totals, rank, n_seg, d_off, d_totals + 1);
     YH_HIP(hipGetLastError());
     return YH_OK;
 }
@@ -400,6 +605,167 @@ extern "C" int yh_sketch_dna(const uint8_t* seq, uint64_t n_bytes, int ksize, ui
         }
     }
     if (rc != YH_OK) { (void)hipStreamSynchronize(c.s_copy); (void)hipStreamSynchronize(c.s_comp); }
+#undef SK_HIP
+    if (c.seq_cap > (1ull << 30)) { (void)hipFree(c.d_seq); c.d_seq = nullptr; c.seq_cap = 0; }
+    return rc;
+}
+
+// ---- the segmented form -------------------------------------------------------------------------------------------------------
+extern "C" uint64_t yh_sketch_segments_work_bytes(uint64_t cap_kept, uint64_t n_seg) {
+    (void)n_seg;  // (the layout depends on the pairs alone; the argument is there so that it may)
+    SegWork w;
+    if (seg_work_layout(std::min<u64>(cap_kept, 0xffffffffull), w) != YH_OK) return 0;
+    return w.total;
+}
+
+extern "C" int yh_sketch_segments_device(const uint8_t* d_seq, uint64_t n_bytes, const uint64_t* d_seg_off, uint64_t n_seg, int ksize,
+                                         uint64_t seed, uint64_t max_hash, uint64_t cap_kept, void* d_work, uint64_t work_bytes,
+                                         uint64_t cap_mins, uint64_t* d_mins, uint32_t* d_abund, uint64_t* d_off, uint64_t* d_totals,
+                                         void* stream) {
+    if (!d_seg_off || !d_off || !d_totals || !d_work || (n_bytes && !d_seq) || (cap_mins && (!d_mins || !d_abund))) {
+        yh_set_error("null argument");
+        return YH_ERR_INVALID_ARG;
+    }
+    YH_TRY(seg_args_ok(n_bytes, n_seg, ksize));
+    hipStream_t st = (hipStream_t)stream;
+    if (n_seg == 0) {
+        YH_HIP(hipMemsetAsync(d_totals, 0, 2 * sizeof(u64), st));
+        YH_HIP(hipMemsetAsync(d_off, 0, sizeof(u64), st));
+        return YH_OK;
+    }
+    cap_kept = std::min<u64>(cap_kept, n_bytes);  // (never more pairs than windows)
+    SegWork w;
+    YH_TRY(seg_work_layout(cap_kept, w));
+    if (work_bytes < w.total) { yh_set_error("work buffer holds %llu bytes, %llu needed", (u64)work_bytes, w.total); return YH_ERR_INVALID_ARG; }
+    u8* work = reinterpret_cast<u8*>((reinterpret_cast<uintptr_t>(d_work) + 255u) & ~(uintptr_t)255u);
+    return seg_finish(d_seq, n_bytes, (const u64*)d_seg_off, (u32)n_seg, (u32)ksize, seed, max_hash, cap_kept, work, w, cap_mins,
+                      (u64*)d_mins, d_abund, (u64*)d_off, (u64*)d_totals, st, false);
+}
+
+extern "C" int yh_sketch_segments(const uint8_t* seq, uint64_t n_bytes, const uint64_t* seg_off, uint64_t n_seg, int ksize, uint64_t seed,
+                                  uint64_t max_hash, int device_id, uint64_t cap_mins, uint64_t* mins_out, uint32_t* abund_out,
+                                  uint64_t* off_out, uint64_t* n_out) {
+    if (!n_out || !seg_off || !off_out || (n_bytes && !seq) || (cap_mins && (!mins_out || !abund_out))) {
+        yh_set_error("null argument");
+        return YH_ERR_INVALID_ARG;
+    }
+    *n_out = 0;
+    YH_TRY(seg_args_ok(n_bytes, n_seg, ksize));
+    if (seg_off[0] != 0 || seg_off[n_seg] != n_bytes) { yh_set_error("segment offsets must start at 0 and end at n_bytes"); return YH_ERR_INVALID_ARG; }
+    for (u64 s = 0; s < n_seg; ++s)
+        if (seg_off[s] > seg_off[s + 1]) { yh_set_error("segment offsets must not descend (segment %llu)", s); return YH_ERR_INVALID_ARG; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        yh_set_error("no HIP device available (libyacht_hip has no CPU fallback)");
+        return YH_ERR_NO_DEVICE;
+    }
+    if (device_id < 0 || device_id >= ndev) { yh_set_error("device_id %d out of range", device_id); return YH_ERR_NO_DEVICE; }
+    YH_HIP(hipSetDevice(device_id));
+    for (u64 s = 0; s <= n_seg; ++s) off_out[s] = 0;
+    if (n_seg == 0 || n_bytes < (uint64_t)ksize) return YH_OK;
+    // As yh_sketch_dna: the sequence goes up in pieces of 32 MiB on one stream while the complete windows are hashed on
+    // another; buffers, streams and events are kept per device between calls.  The pairs get room for 1.25 x the expected
+    // number of kept hashes (+ 4 096); a sequence that keeps more (low complexity) is hashed once more, from HBM, with room
+    // for the count the first pass reported.
+    struct SgCtx { u8* d_seq = nullptr; u64 seq_cap = 0; u64* d_segoff = nullptr; u64 seg_cap = 0; u8* d_work = nullptr; u64 work_cap = 0;
+                   u64* d_mins = nullptr; u32* d_abund = nullptr; u64 out_cap = 0; u64* d_off = nullptr; u64 off_cap = 0; u64* d_tot = nullptr;
+                   hipStream_t s_copy = nullptr, s_comp = nullptr; hipEvent_t ev[2] = {nullptr, nullptr}; };
+    static std::mutex mu;
+    static SgCtx ctxs[64];
+    std::lock_guard<std::mutex> lock(mu);
+    SgCtx& c = ctxs[device_id & 63];
+    int rc = YH_OK;
+#define SK_HIP(call)                                                              \
+    if (rc == YH_OK) {                                                            \
+        hipError_t e__ = (call);                                                  \
+        if (e__ != hipSuccess) {                                                  \
+            yh_set_error("%s failed: %s", #call, hipGetErrorString(e__));         \
+            rc = (e__ == hipErrorOutOfMemory) ? YH_ERR_OOM : YH_ERR_HIP;          \
+        }                                                                         \
+    }
+#define SK_GROW(ptr, have, want, bytes)                                           \
+    if (rc == YH_OK && (have) < (want)) {                                         \
+        if (ptr) (void)hipFree(ptr);                                              \
+        ptr = nullptr; have = 0;                                                  \
+        SK_HIP(hipMalloc((void**)&ptr, (bytes)));                                 \
+        if (rc == YH_OK) have = (want);                                           \
+    }
+    if (!c.s_copy) {
+        SK_HIP(hipStreamCreateWithFlags(&c.s_copy, hipStreamNonBlocking));
+        SK_HIP(hipStreamCreateWithFlags(&c.s_comp, hipStreamNonBlocking));
+        SK_HIP(hipEventCreateWithFlags(&c.ev[0], hipEventDisableTiming));
+        SK_HIP(hipEventCreateWithFlags(&c.ev[1], hipEventDisableTiming));
+        SK_HIP(hipMalloc((void**)&c.d_tot, 2 * sizeof(u64)));
+    }
+    const u64 n_win = n_bytes - (u64)ksize + 1;
+    const double keep = ((double)max_hash + 1.0) / 18446744073709551616.0;
+    u64 cap_kept = std::min<u64>(n_win, (u64)((double)n_win * keep * 1.25) + 4096);
+    SK_GROW(c.d_seq, c.seq_cap, n_bytes, n_bytes + 64);
+    SK_GROW(c.d_segoff, c.seg_cap, n_seg + 1, (n_seg + 1) * sizeof(u64));
+    SK_GROW(c.d_off, c.off_cap, n_seg + 1, (n_seg + 1) * sizeof(u64));
+    u64 totals[2] = {0, 0};
+    for (int pass = 0; pass < 2 && rc == YH_OK; ++pass) {
+        SegWork w;
+        if (rc == YH_OK) rc = seg_work_layout(cap_kept, w);
+        SK_GROW(c.d_work, c.work_cap, w.total, w.total);
+        if (rc == YH_OK && c.out_cap < cap_kept) {
+            if (c.d_mins) (void)hipFree(c.d_mins);
+            if (c.d_abund) (void)hipFree(c.d_abund);
+            c.d_mins = nullptr; c.d_abund = nullptr; c.out_cap = 0;
+            SK_HIP(hipMalloc((void**)&c.d_mins, cap_kept * sizeof(u64)));
+            SK_HIP(hipMalloc((void**)&c.d_abund, cap_kept * sizeof(u32)));
+            if (rc == YH_OK) c.out_cap = cap_kept;
+        }
+        if (rc != YH_OK) break;
+        u8* work = reinterpret_cast<u8*>((reinterpret_cast<uintptr_t>(c.d_work) + 255u) & ~(uintptr_t)255u);
+        const SegArgs sa{c.d_segoff, (u32)n_seg, (u32*)(work + w.seg_a)};
+        SK_HIP(hipMemsetAsync(c.d_tot, 0, 2 * sizeof(u64), c.s_comp));
+        SK_HIP(hipMemsetD32Async((hipDeviceptr_t)sa.out_seg, (int)(u32)n_seg, cap_kept, c.s_comp));
+        if (pass == 0) {
+            SK_HIP(hipMemcpyAsync(c.d_segoff, seg_off, (n_seg + 1) * sizeof(u64), hipMemcpyHostToDevice, c.s_comp));
+            const u64 piece = 32ull << 20;
+            u64 done_win = 0;
+            int flip = 0;
+            for (u64 p0 = 0; p0 < n_bytes && rc == YH_OK; p0 += piece, flip ^= 1) {
+                const u64 p1 = std::min<u64>(n_bytes, p0 + piece);
+                SK_HIP(hipMemcpyAsync(c.d_seq + p0, seq + p0, p1 - p0, hipMemcpyHostToDevice, c.s_copy));
+                SK_HIP(hipEventRecord(c.ev[flip], c.s_copy));
+                SK_HIP(hipStreamWaitEvent(c.s_comp, c.ev[flip], 0));
+                // windows whose bytes are all there, in whole workgroups (the last piece: all that is left)
+                const u64 avail = p1 >= (u64)ksize ? p1 - (u64)ksize + 1 : 0;
+                const u64 upto = (p1 == n_bytes) ? n_win : (avail / SK_WIN_ALIGN) * SK_WIN_ALIGN;
+                if (rc == YH_OK && upto > done_win) {
+                    rc = launch_sketch(c.d_seq, p1, (u32)ksize, seed, max_hash, cap_kept, (u64*)(work + w.hash_a), c.d_tot, c.s_comp, done_win, upto, &sa);
+                    done_win = upto;
+                }
+            }
+        } else if (rc == YH_OK) {
+            rc = launch_sketch(c.d_seq, n_bytes, (u32)ksize, seed, max_hash, cap_kept, (u64*)(work + w.hash_a), c.d_tot, c.s_comp, 0, n_win, &sa);
+        }
+        if (rc == YH_OK)
+            rc = seg_finish(c.d_seq, n_bytes, c.d_segoff, (u32)n_seg, (u32)ksize, seed, max_hash, cap_kept, work, w, cap_kept, c.d_mins, c.d_abund,
+                            c.d_off, c.d_tot, c.s_comp, true);
+        SK_HIP(hipMemcpyAsync(totals, c.d_tot, 2 * sizeof(u64), hipMemcpyDeviceToHost, c.s_comp));
+        SK_HIP(hipStreamSynchronize(c.s_comp));
+        if (rc != YH_OK || totals[0] <= cap_kept) break;
+        if (pass == 1) { yh_set_error("kept hashes changed between two passes"); rc = YH_ERR_HIP; break; }
+        cap_kept = totals[0];
+    }
+    if (rc == YH_OK) {
+        *n_out = totals[1];
+        SK_HIP(hipMemcpyAsync(off_out, c.d_off, (n_seg + 1) * sizeof(u64), hipMemcpyDeviceToHost, c.s_comp));
+        if (cap_mins && totals[1] <= cap_mins && totals[1]) {
+            SK_HIP(hipMemcpyAsync(mins_out, c.d_mins, totals[1] * sizeof(u64), hipMemcpyDeviceToHost, c.s_comp));
+            SK_HIP(hipMemcpyAsync(abund_out, c.d_abund, totals[1] * sizeof(u32), hipMemcpyDeviceToHost, c.s_comp));
+        }
+        SK_HIP(hipStreamSynchronize(c.s_comp));
+        if (rc == YH_OK && cap_mins && totals[1] > cap_mins) {
+            yh_set_error("sketch buffers hold %llu entries, %llu needed", (u64)cap_mins, totals[1]);
+            rc = YH_ERR_CAPACITY;
+        }
+    }
+    if (rc != YH_OK && rc != YH_ERR_CAPACITY) { (void)hipStreamSynchronize(c.s_copy); (void)hipStreamSynchronize(c.s_comp); }
+#undef SK_GROW
 #undef SK_HIP
     if (c.seq_cap > (1ull << 30)) { (void)hipFree(c.d_seq); c.d_seq = nullptr; c.seq_cap = 0; }
     return rc;

@@ -5,7 +5,8 @@ The reference's `yacht sketch ref|sample` are thin wrappers around the third-par
 sketch_sample.py:31-49).  Here the k-mer hashing runs in libyacht_hip.so (yh_sketch_dna) and this
 module does the file handling: FASTA/FASTQ (optionally gzip) in, sourmash-format signatures out
 (yacht_amd.sigio), one signature per file (all records merged) like `sourmash sketch` without
-`--singleton`.
+`--singleton`.  `yacht sketch ref` sends many records or genome files through ONE device call
+(yh_sketch_segments: one segment, one finished sketch each); `yacht sketch sample` does not.
 """
 from __future__ import annotations
 
@@ -101,9 +102,152 @@ def sketch_file(path: str, ksize: int = 31, scaled: int = 1000, name: Optional[s
     return sigio.Signature(mh, name=name, filename=path)
 
 
+# ---- many records per device call (yh_sketch_segments) ----
+SEGMENT_CALL_LIMIT = 2 ** 32          # bytes: a segmented call takes less than this
+DEFAULT_BATCH_BYTES = 256 << 20       # of sequence per call (YACHT_SKETCH_BATCH_BYTES overrides it)
+MAX_READERS = 16
+
+
+def sketch_segments(buf, seg_off, ksize: int, scaled: int, seed: int = DEFAULT_SEED,
+                    device: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """One finished sketch per segment of `buf` in one device call: (mins uint64, abund uint32, off uint64[n_seg + 1]);
+    segment s owns mins[off[s]:off[s + 1]], strictly ascending.  seg_off[n_seg + 1]: ascending byte offsets from 0 to
+    len(buf).  A window counts for the segment its first byte lies in, and only when all its bytes lie inside it."""
+    lib = _lib.load()
+    if isinstance(buf, (bytes, bytearray, memoryview)):
+        buf = np.frombuffer(buf, dtype=np.uint8)
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    off_in = np.ascontiguousarray(seg_off, dtype=np.uint64)
+    if off_in.ndim != 1 or off_in.size < 1:
+        raise ValueError("seg_off needs n_seg + 1 entries")
+    n_seg = off_in.size - 1
+    mh = max_hash_for_scaled(scaled)
+    cap = min(int(buf.size / max(scaled, 1) * 1.5) + 4096, max(int(buf.size), 1))
+    off = np.empty(n_seg + 1, dtype=np.uint64)
+    n = C.c_uint64(0)
+    while True:
+        mins = np.empty(cap, dtype=np.uint64)
+        abund = np.empty(cap, dtype=np.uint32)
+        rc = lib.yh_sketch_segments(C.c_void_p(buf.ctypes.data), buf.size, C.c_void_p(off_in.ctypes.data), n_seg, ksize, seed, mh,
+                                    device, cap, C.c_void_p(mins.ctypes.data), C.c_void_p(abund.ctypes.data),
+                                    C.c_void_p(off.ctypes.data), C.byref(n))
+        if rc == _lib.YH_ERR_CAPACITY:
+            cap = int(n.value)
+            continue
+        _lib.check(rc)
+        return mins[: int(n.value)], abund[: int(n.value)], off
+
+
+def batch_bytes() -> int:
+    v = os.environ.get("YACHT_SKETCH_BATCH_BYTES")
+    return max(int(v), 1) if v else DEFAULT_BATCH_BYTES
+
+
+def use_loop_path() -> bool:
+    """YACHT_SKETCH_REF=loop: one device call per record / per file, for A/B checks against the batched path."""
+    return os.environ.get("YACHT_SKETCH_REF", "") == "loop"
+
+
+def sketch_units(units: Iterable[bytes], ksize: int, scaled: int, seed: int = DEFAULT_SEED, device: int = 0,
+                 budget: Optional[int] = None) -> Iterator[Tuple[np.ndarray, np.ndarray]]:
+    """(mins, abundances) of every unit (one segment each: a record, or a file's records joined by a newline), in order,
+    what sketch_sequences([unit]) gives.  Units are gathered up to `budget` bytes per device call; one that is larger goes
+    alone, and one too large for a segmented call takes the unsegmented path.  `units` is consumed lazily, a batch at a
+    time, so a producer that reads ahead (read_units_ahead) works while the device does."""
+    budget = batch_bytes() if budget is None else budget
+    batch: List[bytes] = []
+    held = 0
+
+    def flush():
+        nonlocal batch, held
+        if not batch:
+            return
+        off = np.zeros(len(batch) + 1, dtype=np.uint64)
+        np.cumsum([len(u) for u in batch], out=off[1:])
+        buf = np.frombuffer(b"".join(batch), dtype=np.uint8) if len(batch) > 1 else np.frombuffer(batch[0], dtype=np.uint8)
+        mins, abund, o = sketch_segments(buf, off, ksize, scaled, seed, device)
+        o = o.astype(np.int64)
+        batch, held = [], 0
+        for s in range(o.size - 1):
+            yield mins[o[s]:o[s + 1]].copy(), abund[o[s]:o[s + 1]].astype(np.int64)
+
+    for u in units:
+        u = bytes(u) if not isinstance(u, bytes) else u
+        if len(u) >= SEGMENT_CALL_LIMIT:
+            yield from flush()
+            yield sketch_sequences([u], ksize, scaled, seed, device)
+            continue
+        if batch and held + len(u) > min(budget, SEGMENT_CALL_LIMIT - 1):
+            yield from flush()
+        batch.append(u)
+        held += len(u)
+    yield from flush()
+
+
+def _read_unit(path: str) -> Tuple[Optional[str], bytes]:
+    """(first record's name, the file's records joined by a newline): a genome file as ONE segment"""
+    records = list(read_sequences(path))
+    return (records[0][0] if records else None), b"\n".join(s for _n, s in records)
+
+
+def read_units_ahead(paths: Sequence[str], budget: int) -> Iterator[Tuple[Optional[str], bytes]]:
+    """_read_unit of every path, in order, read and decompressed by a small thread pool that runs ahead of the consumer by
+    about two batches (judged by file size; a gzip file counts four times): the next batch is read while the device works
+    on the current one (gzip and file reads release the GIL)."""
+    from collections import deque
+    from concurrent.futures import ThreadPoolExecutor
+
+    if not paths:
+        return
+
+    def estimate(p):
+        try:
+            size = os.path.getsize(p)
+        except OSError:
+            size = 0
+        return size * (4 if p.endswith(".gz") else 1)
+
+    with ThreadPoolExecutor(max_workers=min(MAX_READERS, len(paths))) as pool:
+        ahead: deque = deque()
+        in_flight = 0
+        nxt = 0
+        while nxt < len(paths) or ahead:
+            while nxt < len(paths) and (not ahead or in_flight < 2 * budget):
+                est = estimate(paths[nxt])
+                ahead.append((pool.submit(_read_unit, paths[nxt]), est))
+                in_flight += est
+                nxt += 1
+            fut, est = ahead.popleft()
+            in_flight -= est
+            yield fut.result()
+
+
+def sketch_genome_files(named_paths: Sequence[Tuple[Optional[str], str]], ksize: int, scaled: int,
+                        device: int = 0) -> List[sigio.Signature]:
+    """One signature per (name, path), in order -- what sketch_file(path, name=name) gives for each (name None: the first
+    record's header) -- with many files per device call."""
+    if use_loop_path():
+        return [sketch_file(p, ksize, scaled, name=n, device=device) for n, p in named_paths]
+    budget = batch_bytes()
+    first_names: List[Optional[str]] = []
+
+    def units():
+        for first, joined in read_units_ahead([p for _n, p in named_paths], budget):
+            first_names.append(first)
+            yield joined
+
+    sigs = []
+    for i, (mins, ab) in enumerate(sketch_units(units(), ksize, scaled, device=device, budget=budget)):
+        name, path = named_paths[i]
+        if name is None:
+            name = first_names[i] if first_names[i] is not None else os.path.basename(path)
+        sigs.append(sigio.Signature(sigio.MinHash(mins, ksize, max_hash_for_scaled(scaled), ab, seed=DEFAULT_SEED), name=name, filename=path))
+    return sigs
+
+
 def sketch_files(paths: Sequence[str], out_zip: str, ksize: int = 31, scaled: int = 1000, device: int = 0) -> List[sigio.Signature]:
     """`yacht sketch ref`-style: one signature per genome file, written as a sourmash .sig.zip."""
-    sigs = [sketch_file(p, ksize, scaled, device=device) for p in paths]
+    sigs = sketch_genome_files([(None, p) for p in paths], ksize, scaled, device=device)
     sigio.write_sig_zip(sigs, out_zip)
     return sigs
 
@@ -121,13 +265,16 @@ def add_ref_arguments(parser) -> None:
 
 def main_ref(args) -> None:
     """A file: one signature per record (the reference passes --singleton).  A folder: one
-    signature per genome file found under it, named by the file name without its suffix."""
+    signature per genome file found under it, named by the file name without its suffix.  Either way many records or
+    files go through one device call (sketch_units); YACHT_SKETCH_REF=loop keeps one call per record / per file."""
     if os.path.isfile(args.infile):
-        sigs = []
-        for name, seq in read_sequences(args.infile):
-            mins, ab = sketch_sequences([seq], args.kmer, args.scaled)
-            sigs.append(sigio.Signature(sigio.MinHash(mins, args.kmer, max_hash_for_scaled(args.scaled), ab), name=name,
-                                        filename=args.infile))
+        records = list(read_sequences(args.infile))
+        if use_loop_path():
+            sketches = (sketch_sequences([seq], args.kmer, args.scaled) for _name, seq in records)
+        else:
+            sketches = sketch_units((seq for _name, seq in records), args.kmer, args.scaled)
+        sigs = [sigio.Signature(sigio.MinHash(mins, args.kmer, max_hash_for_scaled(args.scaled), ab), name=name, filename=args.infile)
+                for (name, _seq), (mins, ab) in zip(records, sketches)]
     elif os.path.isdir(args.infile):
         found = []
         for root, _dirs, files in os.walk(args.infile):
@@ -136,7 +283,7 @@ def main_ref(args) -> None:
                     if f.endswith(suf):
                         found.append((f[: -len(suf)], os.path.join(root, f)))
                         break
-        sigs = [sketch_file(p, args.kmer, args.scaled, name=n) for n, p in sorted(found)]
+        sigs = sketch_genome_files(sorted(found), args.kmer, args.scaled)
     else:
         raise FileNotFoundError(f"Input path {args.infile} does not exist.")
     sigio.write_sig_zip(sigs, args.outfile)
