@@ -32,15 +32,16 @@ constexpr int WAVE = 64;
 
 // ---- validation + extent ----------------------------------------------------------------------
 // One wave per reference: flag[0] |= 1 if the slice is not strictly ascending; atomicMax of the
-// last element gives the database's largest hash; sizes[j] = |R_j|.
-__global__ void k_scan_refs(const u64* __restrict__ values, const u64* __restrict__ offsets, u64 n_refs,
+// last element gives the database's largest hash; sizes[j] = |R_j|.  n_values = the length of values[] (the CSR's last
+// offset): an offset beyond it is flagged like one below its predecessor, and nothing is read through it.
+__global__ void k_scan_refs(const u64* __restrict__ values, const u64* __restrict__ offsets, u64 n_refs, u64 n_values,
                             u32* __restrict__ sizes, u32* __restrict__ flag, u64* __restrict__ maxv) {
     const u64 wave = (blockIdx.x * (u64)blockDim.x + threadIdx.x) / WAVE;
     const u64 n_waves = ((u64)gridDim.x * blockDim.x) / WAVE;
     const int lane = threadIdx.x & (WAVE - 1);
     for (u64 j = wave; j < n_refs; j += n_waves) {
         const u64 b = offsets[j], e = offsets[j + 1];
-        bool bad = e < b;
+        bool bad = e < b || e > n_values;
         if (!bad) {
             for (u64 k = b + lane; k + 1 < e; k += WAVE)
                 if (!(values[k] < values[k + 1])) bad = true;
@@ -89,13 +90,14 @@ __device__ __forceinline__ u32 block_excl_scan(u32 v, u32* total_out, u32* lds /
 }
 
 // ---- index build ---------------------------------------------------------------------------------
-// (offsets: the entries of the references [ref_base, ref_base + n_refs); ids: indexed like values)
-__global__ void k_fill_ref_ids(const u64* __restrict__ offsets, u64 n_refs, u32* __restrict__ ids, u32 ref_base = 0) {
+// (offsets: the entries of the references [ref_base, ref_base + n_refs); ids: indexed like values, n_ids of them -- a chunk of
+// an upload gets its ids before the verdict on its offsets is back, so an end beyond the array is cut here)
+__global__ void k_fill_ref_ids(const u64* __restrict__ offsets, u64 n_refs, u32* __restrict__ ids, u64 n_ids, u32 ref_base = 0) {
     const u64 wave = (blockIdx.x * (u64)blockDim.x + threadIdx.x) / WAVE;
     const u64 n_waves = ((u64)gridDim.x * blockDim.x) / WAVE;
     const int lane = threadIdx.x & (WAVE - 1);
     for (u64 j = wave; j < n_refs; j += n_waves) {
-        const u64 b = offsets[j], e = offsets[j + 1];
+        const u64 b = offsets[j], e = min(offsets[j + 1], n_ids);
         for (u64 k = b + lane; k < e; k += WAVE) ids[k] = ref_base + (u32)j;
     }
 }
@@ -462,8 +464,8 @@ static int validate_begin(yh_db* db) {
 static int validate_refs(yh_db* db, const u64* d_values, const u64* d_offsets, u64 r0, u64 r1) {
     if (r1 > r0) {
         u64* d_maxv = (u64*)(db->d_flag + 2);  // 8-byte aligned slot inside the 16-byte scratch
-        k_scan_refs<<<grid_for((r1 - r0) * WAVE, 256), 256, 0, db->stream>>>(d_values, d_offsets + r0, r1 - r0, db->d_sizes + r0,
-                                                                            db->d_flag, d_maxv);
+        k_scan_refs<<<grid_for((r1 - r0) * WAVE, 256), 256, 0, db->stream>>>(d_values, d_offsets + r0, r1 - r0, db->n_hashes,
+                                                                            db->d_sizes + r0, db->d_flag, d_maxv);
         YH_HIP(hipGetLastError());
     }
     return YH_OK;
@@ -522,10 +524,11 @@ int yh_build_validate(yh_db* db, const u64* d_values, const u64* d_offsets) {
 // the sort's first level does on its way through (yh_psort_check_order) or, without that sort, yh_build_check_order.
 __global__ void k_ref_extents(const u64* __restrict__ values, const u64* __restrict__ offsets, u64 n_refs, u32* __restrict__ sizes,
                               u32* __restrict__ flag, u64* __restrict__ maxv) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) { maxv[1] = offsets[0]; maxv[2] = offsets[n_refs]; }
+    const u64 last = offsets[n_refs];  // (uniform) the length of values[]: an offset beyond it is refused before anything is read through it
+    if (blockIdx.x == 0 && threadIdx.x == 0) { maxv[1] = offsets[0]; maxv[2] = last; }
     for (u64 j = blockIdx.x * (u64)blockDim.x + threadIdx.x; j < n_refs; j += (u64)gridDim.x * blockDim.x) {
         const u64 b = offsets[j], e = offsets[j + 1];
-        if (e < b) { atomicOr(flag, 1u); continue; }
+        if (e < b || e > last) { atomicOr(flag, 1u); continue; }
         const u64 n = e - b;
         sizes[j] = (u32)n;
         if (n > 0xffffffffull) atomicOr(flag, 2u);
@@ -715,11 +718,18 @@ static int upload_sorted_impl(yh_db* db, const u64* h_values, const u64* h_offse
     }
     rb.push_back(N);
     const size_t C = rb.size() - 1;
+    // the chunk boundaries size the copies out of the caller's array: each inside [its predecessor, H] before a byte moves (the
+    // offsets between them are the device's to judge -- k_scan_refs reads nothing through an offset above H)
+    for (size_t c = 0; c < C; ++c)
+        if (h_offsets[rb[c]] > h_offsets[rb[c + 1]] || h_offsets[rb[c + 1]] > H) {
+            yh_set_error("a reference sketch is not strictly ascending (or offsets are not monotone)");
+            return YH_ERR_UNSORTED;
+        }
     u64 max_last = 0;
     if (pk) max_last = pk->max_hash;  // (the packer's; a wrong one shows below: the largest hash the check finds must not exceed it)
     else
         for (u64 j = 0; j < N; ++j)
-            if (h_offsets[j + 1] > h_offsets[j]) max_last = std::max(max_last, h_values[h_offsets[j + 1] - 1]);
+            if (h_offsets[j + 1] > h_offsets[j] && h_offsets[j + 1] <= H) max_last = std::max(max_last, h_values[h_offsets[j + 1] - 1]);
     double t_prev = trace_now();
     TRACE("chunk plan + max");
     // (the upload stream and the chunk events are made once per device and kept: a dozen creates and destroys were
@@ -830,7 +840,7 @@ static int upload_sorted_impl(yh_db* db, const u64* h_values, const u64* h_offse
         } else if (rc == YH_OK && n && fused) {
             rc = yh_psort_add(db, ps, d_values + e0, nullptr, n, e0);  // (the value of a pair is its position)
         } else if (rc == YH_OK && n) {
-            k_fill_ref_ids<<<grid_for((r1 - r0) * WAVE, 256), 256, 0, st>>>(d_offsets + r0, r1 - r0, d_ids, (u32)r0);
+            k_fill_ref_ids<<<grid_for((r1 - r0) * WAVE, 256), 256, 0, st>>>(d_offsets + r0, r1 - r0, d_ids, H, (u32)r0);
             if (ps) rc = yh_psort_add(db, ps, d_values + e0, d_ids + e0, n);  // this chunk's pairs into the first-level regions
         }
         UP_HIP(hipEventRecord(ee[c], st));
@@ -860,7 +870,7 @@ static int upload_sorted_impl(yh_db* db, const u64* h_values, const u64* h_offse
             UP_HIP(yh_tmalloc(db, (void**)&K[0], H * sizeof(u64)));
             UP_HIP(yh_tmalloc(db, (void**)&V[0], H * sizeof(u32)));
             UP_HIP(yh_tmalloc(db, (void**)&d_ids, H * sizeof(u32)));
-            if (rc == YH_OK) k_fill_ref_ids<<<grid_for(N * WAVE, 256), 256, 0, st>>>(d_offsets, N, d_ids);
+            if (rc == YH_OK) k_fill_ref_ids<<<grid_for(N * WAVE, 256), 256, 0, st>>>(d_offsets, N, d_ids, H);
         }
     }
     if (rc == YH_OK && ps) rc = yh_psort_finish(db, ps, K[0], V[0], &sorted);  // second level + bucket sorts
@@ -1088,7 +1098,7 @@ int yh_build_index(yh_db* db, const u64* d_values, const u64* d_offsets, u64* d_
                 yh_psort_chunks(ps, &nb, &d_chunk_off, &d_chunk_counts);
             }
         }
-        if (rc == YH_OK && !sorted) k_fill_ref_ids<<<grid_for(N * WAVE, 256), 256, 0, st>>>(d_offsets, N, d_ids);
+        if (rc == YH_OK && !sorted) k_fill_ref_ids<<<grid_for(N * WAVE, 256), 256, 0, st>>>(d_offsets, N, d_ids, H);
         if (rc == YH_OK && try_psort && !sorted) {
             bool unsorted = false;
             rc = yh_psort_begin(db, H, db->max_hash, &ps);

@@ -881,6 +881,7 @@ struct PieceArgs {
     const u64* values;
     const u64* off;      // CSR offsets [N + 1]
     u64 n_refs;
+    u64 n_values;        // length of values[] (H): a sketch that ends beyond it is flagged, not read (k_piece_bounds)
     u32* bnd;            // [(P1 + 1)][n_pad]: bnd[r][i] = first position of sketch i whose region is >= r (bnd[0][i] = off[i], bnd[P1][i] = off[i + 1])
     u64 n_pad;
     u32 P1, P2, S, Gn, SK;
@@ -909,7 +910,7 @@ __global__ void __launch_bounds__(PC_BOUND_THREADS) k_piece_bounds(const PieceAr
     for (u32 s = wv; s < nsk; s += nwv) {  // (wave-uniform)
         u32* row = bl + (size_t)s * W;
         const u64 b = a.off[i0 + s], e = a.off[i0 + s + 1];
-        if (e < b) { bad = true; for (u32 r = lane; r < W; r += 64) row[r] = (u32)b; continue; }
+        if (e < b || e > a.n_values) { bad = true; for (u32 r = lane; r < W; r += 64) row[r] = (u32)min(b, a.n_values); continue; }
         u32 carry_reg = 0xffffffffu;  // region of the element in front (none yet: -1)
         u64 carry_h = 0;
         bool have = false;
@@ -1096,7 +1097,7 @@ __global__ void __launch_bounds__(256) k_spill_collect(const PieceArgs a) {
     const u64 b0 = a.off[sk], e0 = a.off[sk + 1];
     const u64 rem_mask = (1ull << a.rem_bits) - 1ull;
     auto marked = [&](u64 h) -> u32 {  // the pair's bucket when that bucket is marked, else ~0
-        const u32 bk = bucket_of(h, a.lsh, a.mul);
+        const u32 bk = min(bucket_of(h, a.lsh, a.mul), a.P1 * a.P2 - 1u);  // (a key above max_hash: stay inside the bit map)
         return ((a.over_bits[bk >> 5] >> (bk & 31u)) & 1u) ? bk : 0xffffffffu;
     };
     // Two walks over the sketch: the first COUNTS the wave's pairs of marked buckets, ONE atomic reserves their room, the second
@@ -1199,13 +1200,13 @@ __global__ void __launch_bounds__(256) k_spill_group(const u64* __restrict__ key
 // the side list of a SORTING handle, sorted by (hash, reference): every pair back to its bucket's place in the output, and the
 // bucket's run statistics (what k_bucket_sort leaves for the buckets it sorts itself)
 __global__ void __launch_bounds__(256) k_spill_place(const u64* __restrict__ key /* sorted */, const u32* __restrict__ ref, u64 n, u32 lsh, u64 mul_fine,
-                                                     const u64* __restrict__ off, u64* __restrict__ out_k, u32* __restrict__ out_v, u32* __restrict__ counts) {
+                                                     u32 nb, const u64* __restrict__ off, u64* __restrict__ out_k, u32* __restrict__ out_v, u32* __restrict__ counts) {
     const u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x;
     if (i >= n) return;
     const u64 h = key[i];
-    const u32 b = bucket_of(h, lsh, mul_fine);
+    const u32 b = min(bucket_of(h, lsh, mul_fine), nb - 1u);  // (a key above max_hash: stay inside off[] / counts[])
     u64 lo = 0, hi = i;  // the first entry of bucket b (buckets are monotone in the hash)
-    while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (bucket_of(key[mid], lsh, mul_fine) < b) lo = mid + 1; else hi = mid; }
+    while (lo < hi) { const u64 mid = (lo + hi) >> 1; if (min(bucket_of(key[mid], lsh, mul_fine), nb - 1u) < b) lo = mid + 1; else hi = mid; }
     const u64 dst = off[b] + (i - lo);
     out_k[dst] = h;
     out_v[dst] = ref[i];
@@ -1618,7 +1619,7 @@ int yh_pc_begin(yh_db* db, u64 H, u64 max_hash, u64 n_refs, u64* d_rec, yh_piece
 // (the pairwise records are not cleared anywhere on this path: k_bucket_group5 and k_spill_group write every position's record)
 static PieceArgs pc_args(const yh_pieces* s, const u64* d_values, const u64* d_offsets) {
     PieceArgs a{};
-    a.values = d_values; a.off = d_offsets; a.n_refs = s->n_refs; a.bnd = s->bnd; a.n_pad = s->n_pad;
+    a.values = d_values; a.off = d_offsets; a.n_refs = s->n_refs; a.n_values = s->H; a.bnd = s->bnd; a.n_pad = s->n_pad;
     a.P1 = s->P1; a.P2 = s->P2; a.S = s->S; a.Gn = s->Gn; a.SK = s->SK;
     a.mul = s->mul_fine; a.lsh = s->lsh; a.rem_bits = s->rem_bits; a.inv_p2 = s->inv_p2;
     a.out_a = s->a2; a.out_p = s->p2; a.out_cnt = s->cnt; a.flags = s->cnt + s->NB;
@@ -1840,7 +1841,7 @@ int yh_pc_sort(yh_db* db, const u64* d_values, const u64* d_offsets, u64 n_refs,
                 rc = yh_radix_sort_pairs_u64_u32(db, k1, k2, r1, r2, n_spill, hbits);  // stable: equal hashes keep ascending references
             }
             if (rc == YH_OK) {
-                k_spill_place<<<(u32)((n_spill + 255) / 256), 256, 0, db->stream>>>(k2, r2, n_spill, s->lsh, s->mul_fine, off, d_keys_out, d_vals_out, counts);
+                k_spill_place<<<(u32)((n_spill + 255) / 256), 256, 0, db->stream>>>(k2, r2, n_spill, s->lsh, s->mul_fine, (u32)s->NB, off, d_keys_out, d_vals_out, counts);
                 if (hipGetLastError() != hipSuccess || hipStreamSynchronize(db->stream) != hipSuccess) rc = YH_ERR_HIP;
             }
             yh_tfree(db, k1); yh_tfree(db, k2); yh_tfree(db, r1); yh_tfree(db, r2);
