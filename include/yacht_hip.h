@@ -946,6 +946,48 @@ int yh_sketch_segments(const uint8_t* seq, uint64_t n_bytes, const uint64_t* seg
                        uint64_t max_hash, int device_id, uint64_t cap_mins, uint64_t* mins_out, uint32_t* abund_out,
                        uint64_t* off_out, uint64_t* n_out);
 
+/* ---- the sketch accumulator: ONE sketch with abundances out of many chunks (additive to ABI 8) ----
+ * What `yacht sketch sample` needs for read files of any size: the files are parsed on the host and handed over chunk by
+ * chunk; the distinct kept hashes and their counts stay in HBM between the calls.  A CHUNK is what yh_sketch_dna takes --
+ * records separated by a byte that is not a base -- and chunks are independent: no window spans two calls, a chunk of fewer
+ * than ksize bytes adds nothing.
+ * THE CONTRACT (chunking invariance): the result depends only on the multiset of kept hashes -- not on how the bytes were
+ * cut into chunks (at record boundaries), not on cap_entries, not on when the state was compacted.  The same input gives the
+ * same bytes.  Counts are 64-bit throughout: nothing saturates.
+ * The state is a log of `capacity` (hash, count) entries: [0, n_compacted) strictly ascending distinct hashes with their
+ * counts, [n_compacted, n_entries) raw kept hashes in arrival order (count 1).  A chunk's hashes are written straight behind
+ * the tail; the host reads their number (one synchronize per chunk).  A log that is full is COMPACTED -- radix sort over the
+ * bits of max_hash, head flags, one scan for the ranks, one 64-bit scan for the counts, one write; no atomics, no hash table,
+ * a k-mer seen a million times costs what a singleton costs -- and, when fewer than D entries stay free behind the D
+ * distinct ones, doubled.  A chunk that keeps more than the free entries counts for nothing at first: the log is compacted
+ * and grown to the reported number and the chunk, still in HBM, is hashed once more (n_rehashed_chunks).
+ * The handle owns its stream and its buffers (nothing is shared with yh_sketch_dna); one call at a time per handle, every
+ * call returns with its work done.  At most 2^32 - 2 entries (YH_ERR_UNSUPPORTED beyond).
+ *
+ * yh_sketch_acc_create         cap_entries: the log's first capacity, 0 = the default (2^21); ksize 1..255
+ * yh_sketch_acc_destroy        NULL is fine
+ * yh_sketch_acc_add            a chunk in host memory, uploaded in pieces under the hashing as yh_sketch_dna does
+ * yh_sketch_acc_add_device     a chunk that is already in HBM (complete when the call is made)
+ * yh_sketch_acc_add_hashes     (hash, count) pairs from host arrays, counts = NULL: 1 each; a hash above max_hash is refused
+ *                              (YH_ERR_INVALID_ARG, nothing added); n = 0 adds nothing
+ * yh_sketch_acc_get_info       n_bytes / n_kept: bytes and kept hashes (add_hashes: pairs) taken so far
+ * yh_sketch_acc_finish         compacts, then the distinct hashes strictly ascending with their summed counts; *n_out their
+ *                              number; two-call sizing: cap = 0 only counts, YH_ERR_CAPACITY (with *n_out set) when cap is too
+ *                              small.  The accumulator goes on: more chunks may follow, a later finish includes them.
+ * yh_sketch_acc_finish_device  the same as pointers into the state, valid until the next call on the handle              */
+typedef struct yh_sketch_acc yh_sketch_acc;
+typedef struct yh_sketch_acc_info {
+    uint64_t n_bytes, n_kept, n_entries, n_compacted, capacity, n_compactions, n_rehashed_chunks;
+} yh_sketch_acc_info;
+int yh_sketch_acc_create(int device_id, int ksize, uint64_t seed, uint64_t max_hash, uint64_t cap_entries, yh_sketch_acc** out);
+int yh_sketch_acc_destroy(yh_sketch_acc* acc);
+int yh_sketch_acc_add(yh_sketch_acc* acc, const uint8_t* seq, uint64_t n_bytes);
+int yh_sketch_acc_add_device(yh_sketch_acc* acc, const uint8_t* d_seq, uint64_t n_bytes);
+int yh_sketch_acc_add_hashes(yh_sketch_acc* acc, const uint64_t* hashes, const uint64_t* counts, uint64_t n);
+int yh_sketch_acc_get_info(yh_sketch_acc* acc, yh_sketch_acc_info* info);
+int yh_sketch_acc_finish(yh_sketch_acc* acc, uint64_t cap, uint64_t* mins_out, uint64_t* abund_out, uint64_t* n_out);
+int yh_sketch_acc_finish_device(yh_sketch_acc* acc, const uint64_t** d_mins, const uint64_t** d_abund, uint64_t* n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,11 @@ class Timing(C.Structure):
     ]
 
 
+class SketchAccInfo(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_bytes", "n_kept", "n_entries", "n_compacted", "capacity", "n_compactions",
+                                          "n_rehashed_chunks")]
+
+
 _u64p = C.POINTER(C.c_uint64)
 _u32p = C.POINTER(C.c_uint32)
 _u8p = C.POINTER(C.c_uint8)
@@ -195,6 +200,14 @@ SIGNATURES = {
                                             C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "yh_sketch_segments": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, _vp, _vp,
                                      _vp, C.POINTER(C.c_uint64)]),
+    "yh_sketch_acc_create": (C.c_int, [C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(_vp)]),
+    "yh_sketch_acc_destroy": (C.c_int, [_vp]),
+    "yh_sketch_acc_add": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "yh_sketch_acc_add_device": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "yh_sketch_acc_add_hashes": (C.c_int, [_vp, _vp, _vp, C.c_uint64]),
+    "yh_sketch_acc_get_info": (C.c_int, [_vp, C.POINTER(SketchAccInfo)]),
+    "yh_sketch_acc_finish": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_uint64)]),
+    "yh_sketch_acc_finish_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_uint64)]),
     "yh_hyp_test": (C.c_int, [C.c_uint64, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "yh_train_select": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.POINTER(C.c_uint64)]),
     "yh_sig_batch_read": (C.c_int, [C.POINTER(C.c_char_p), C.c_uint64, C.c_int, C.POINTER(_vp)]),

@@ -509,6 +509,47 @@ static int seg_finish(const u8* d_seq, u64 n_bytes, const u64* d_seg_off, u32 n_
     return YH_OK;
 }
 
+// ---- the accumulator's compaction (yh_sketch_acc*, at the end of the file) -----------------------------------------------------
+// n (key, count) pairs sorted by key -> one pair per distinct key with the counts summed.  As above: k_acc_heads flags the
+// first pair of every run of equal keys (and puts a zero behind the last flag and the last count), one exclusive scan of
+// the flags is every run's rank, one exclusive u64 scan of the counts gives pre[0 .. n], k_acc_emit writes a run's key at its
+// rank and pre[end] - pre[begin] as its count.  One lane per pair; no lane walks a run, no atomic decides a position.
+__global__ void __launch_bounds__(SG_THREADS) k_acc_ones(u64* __restrict__ cnt, u64 n) {
+    const u64 i = (u64)blockIdx.x * SG_THREADS + threadIdx.x;
+    if (i < n) cnt[i] = 1ull;
+}
+
+// (flag and cnt have n + 1 entries)
+__global__ void __launch_bounds__(SG_THREADS) k_acc_heads(const u64* __restrict__ key, u64 n, u32* __restrict__ flag, u64* __restrict__ cnt) {
+    const u64 i = (u64)blockIdx.x * SG_THREADS + threadIdx.x;
+    if (i > n) return;
+    if (i == n) { flag[i] = 0u; cnt[i] = 0ull; return; }
+    flag[i] = (i == 0 || key[i] != key[i - 1]) ? 1u : 0u;
+}
+
+__global__ void __launch_bounds__(SG_THREADS) k_acc_emit(const u64* __restrict__ key, u64 n, const u32* __restrict__ flag,
+                                                         const u32* __restrict__ rank, const u64* __restrict__ pre,
+                                                         u64* __restrict__ key_out, u64* __restrict__ cnt_out) {
+    const u64 i = (u64)blockIdx.x * SG_THREADS + threadIdx.x;
+    if (i >= n || !flag[i]) return;
+    const u64 h = key[i];
+    // the end of the run: the first pair behind i with another key (gallop, then bisect; most runs have one pair)
+    u64 lo = i, step = 1;     // (lo: known equal)
+    u64 hi = n;               // (hi: known different, or n)
+    while (lo + step < n) {
+        if (key[lo + step] != h) { hi = lo + step; break; }
+        lo += step;
+        step <<= 1;
+    }
+    while (lo + 1 < hi) {
+        const u64 m = lo + (hi - lo) / 2;
+        if (key[m] == h) lo = m; else hi = m;
+    }
+    const u64 r = rank[i];    // (r <= i)
+    key_out[r] = h;
+    cnt_out[r] = pre[hi] - pre[i];
+}
+
 }  // namespace
 
 // device buffers, enqueued on `stream`: *d_count is zeroed first and receives the number of kept hashes (which may exceed
@@ -769,4 +810,310 @@ extern "C" int yh_sketch_segments(const uint8_t* seq, uint64_t n_bytes, const ui
 #undef SK_HIP
     if (c.seq_cap > (1ull << 30)) { (void)hipFree(c.d_seq); c.d_seq = nullptr; c.seq_cap = 0; }
     return rc;
+}
+
+// ---- the accumulator: one sketch with abundances out of many chunks -----------------------------------------------------------
+// The state is a LOG: key[capacity] / cnt[capacity]; entries [0, n_compacted) are strictly ascending distinct hashes with their
+// counts, entries [n_compacted, n_entries) raw kept hashes in arrival order.  A chunk is hashed by launch_sketch straight
+// behind the tail; a full log is compacted (sort by key, flag / scan / emit: k_acc_* above) and, when fewer than D entries
+// stay free behind the D distinct ones, doubled.  Counts of raw entries are implied (1) and written only when a compaction
+// or yh_sketch_acc_add_hashes needs them: cnt is valid in [0, n_filled).  The result depends on the multiset of kept hashes
+// alone -- not on the chunking, the capacity or the moments of compaction.  One call at a time per handle.
+constexpr u64 ACC_DEFAULT_CAP = 1ull << 21;
+constexpr u64 ACC_MAX_CAP = 0xfffffffeull;  // (flags and ranks are 32-bit words, one more than the entries)
+
+struct yh_sketch_acc {
+    int device = -1;
+    u32 k = 0;
+    u64 seed = 0, max_hash = 0;
+    hipStream_t s_copy = nullptr, s_comp = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    u64* key = nullptr;
+    u64* cnt = nullptr;
+    u64 capacity = 0, n_entries = 0, n_compacted = 0, n_filled = 0;
+    // scratch of a compaction, for work_cap pairs: the sorted pairs, flags, ranks, prefix sums (+ 1 each), rocPRIM's storage
+    u8* work = nullptr;
+    u64 work_cap = 0;
+    u64 *key_b = nullptr, *cnt_b = nullptr, *pre = nullptr;
+    u32 *flag = nullptr, *rank = nullptr;
+    void* tmp = nullptr;
+    u64 tmp_bytes = 0;
+    u8* d_seq = nullptr;   // the chunk of a host-form add
+    u64 seq_cap = 0;
+    u64* d_cnt = nullptr;  // the hashing kernels' append counter
+    u64 n_bytes = 0, n_kept = 0, n_compactions = 0, n_rehashed = 0;
+};
+
+static bool acc_ok(yh_sketch_acc* a) {
+    if (!a) { yh_set_error("null yh_sketch_acc handle"); return false; }
+    return true;
+}
+
+static u32 acc_blocks(u64 n) { return (u32)((n + SG_THREADS - 1) / SG_THREADS); }
+
+// key / cnt for newcap entries, the first n_entries kept
+static int acc_grow(yh_sketch_acc* a, u64 newcap) {
+    if (newcap > ACC_MAX_CAP) { yh_set_error("the accumulator holds at most %llu entries", ACC_MAX_CAP); return YH_ERR_UNSUPPORTED; }
+    newcap = std::max<u64>(newcap, 1);
+    u64 *nk = nullptr, *nc = nullptr;
+    YH_HIP(hipMalloc((void**)&nk, newcap * sizeof(u64)));
+    hipError_t e = hipMalloc((void**)&nc, newcap * sizeof(u64));
+    if (e == hipSuccess && a->n_entries) {
+        e = hipMemcpyAsync(nk, a->key, a->n_entries * sizeof(u64), hipMemcpyDeviceToDevice, a->s_comp);
+        if (e == hipSuccess && a->n_filled) e = hipMemcpyAsync(nc, a->cnt, a->n_filled * sizeof(u64), hipMemcpyDeviceToDevice, a->s_comp);
+        if (e == hipSuccess) e = hipStreamSynchronize(a->s_comp);
+    }
+    if (e != hipSuccess) {
+        (void)hipFree(nk);
+        if (nc) (void)hipFree(nc);
+        yh_set_error("growing the accumulator to %llu entries failed: %s", newcap, hipGetErrorString(e));
+        return (e == hipErrorOutOfMemory) ? YH_ERR_OOM : YH_ERR_HIP;
+    }
+    if (a->key) (void)hipFree(a->key);
+    if (a->cnt) (void)hipFree(a->cnt);
+    a->key = nk; a->cnt = nc; a->capacity = newcap;
+    return YH_OK;
+}
+
+// the scratch arrays for `pairs` pairs
+static int acc_work(yh_sketch_acc* a, u64 pairs) {
+    if (a->work_cap >= pairs) return YH_OK;
+    if (a->work) (void)hipFree(a->work);
+    a->work = nullptr; a->work_cap = 0;
+    auto up = [](u64 x) { return (x + 255ull) & ~255ull; };
+    const u64 b64 = up((pairs + 1) * sizeof(u64)), b32 = up((pairs + 1) * sizeof(u32));
+    YH_HIP(hipMalloc((void**)&a->work, 3 * b64 + 2 * b32));
+    a->key_b = (u64*)a->work;
+    a->cnt_b = (u64*)(a->work + b64);
+    a->pre = (u64*)(a->work + 2 * b64);
+    a->flag = (u32*)(a->work + 3 * b64);
+    a->rank = (u32*)(a->work + 3 * b64 + b32);
+    a->work_cap = pairs;
+    return YH_OK;
+}
+
+// The log -> distinct ascending hashes with summed counts (n_entries = n_compacted afterwards); then the growth rule: at
+// least as many free entries as distinct ones.  One synchronize (the number of distinct hashes comes back).
+static int acc_compact(yh_sketch_acc* a) {
+    const u64 n = a->n_entries;
+    if (n == a->n_compacted) return YH_OK;
+    hipStream_t st = a->s_comp;
+    YH_TRY(acc_work(a, a->capacity));
+    size_t t1 = 0, t2 = 0, t3 = 0;
+    const u32 bits = bits_of(a->max_hash);
+    YH_HIP(rocprim::radix_sort_pairs(nullptr, t1, (const u64*)nullptr, (u64*)nullptr, (const u64*)nullptr, (u64*)nullptr, (size_t)n, 0u, bits, st));
+    YH_HIP(rocprim::exclusive_scan(nullptr, t2, (const u32*)nullptr, (u32*)nullptr, 0u, (size_t)n + 1, rocprim::plus<u32>(), st));
+    YH_HIP(rocprim::exclusive_scan(nullptr, t3, (const u64*)nullptr, (u64*)nullptr, (u64)0, (size_t)n + 1, rocprim::plus<u64>(), st));
+    const u64 need = std::max<u64>(std::max<u64>(t1, t2), std::max<u64>(t3, 256));
+    if (a->tmp_bytes < need) {
+        if (a->tmp) (void)hipFree(a->tmp);
+        a->tmp = nullptr; a->tmp_bytes = 0;
+        YH_HIP(hipMalloc(&a->tmp, need));
+        a->tmp_bytes = need;
+    }
+    if (a->n_filled < n) k_acc_ones<<<acc_blocks(n - a->n_filled), SG_THREADS, 0, st>>>(a->cnt + a->n_filled, n - a->n_filled);
+    size_t tb = a->tmp_bytes;
+    YH_HIP(rocprim::radix_sort_pairs(a->tmp, tb, (const u64*)a->key, a->key_b, (const u64*)a->cnt, a->cnt_b, (size_t)n, 0u, bits, st));
+    k_acc_heads<<<acc_blocks(n + 1), SG_THREADS, 0, st>>>(a->key_b, n, a->flag, a->cnt_b);
+    tb = a->tmp_bytes;
+    YH_HIP(rocprim::exclusive_scan(a->tmp, tb, (const u32*)a->flag, a->rank, 0u, (size_t)n + 1, rocprim::plus<u32>(), st));
+    tb = a->tmp_bytes;
+    YH_HIP(rocprim::exclusive_scan(a->tmp, tb, (const u64*)a->cnt_b, a->pre, (u64)0, (size_t)n + 1, rocprim::plus<u64>(), st));
+    k_acc_emit<<<acc_blocks(n), SG_THREADS, 0, st>>>(a->key_b, n, a->flag, a->rank, a->pre, a->key, a->cnt);
+    YH_HIP(hipGetLastError());
+    u32 distinct = 0;
+    YH_HIP(hipMemcpyAsync(&distinct, a->rank + n, sizeof(u32), hipMemcpyDeviceToHost, st));
+    YH_HIP(hipStreamSynchronize(st));
+    a->n_entries = a->n_compacted = a->n_filled = distinct;
+    ++a->n_compactions;
+    if (a->capacity - distinct < distinct) YH_TRY(acc_grow(a, std::max<u64>(2ull * distinct, std::min<u64>(2 * a->capacity, ACC_MAX_CAP))));
+    return YH_OK;
+}
+
+// compacted, with room for `more` entries behind the D distinct ones (and for D, as after every compaction)
+static int acc_make_room(yh_sketch_acc* a, u64 more) {
+    YH_TRY(acc_compact(a));
+    const u64 need = a->n_entries + std::max<u64>(more, a->n_entries);
+    if (a->capacity < need) YH_TRY(acc_grow(a, need > ACC_MAX_CAP ? need : std::max<u64>(need, std::min<u64>(2 * a->capacity, ACC_MAX_CAP))));
+    return YH_OK;
+}
+
+// The chunk's kept hashes behind the log's tail; *total = how many there are (more than the free entries: not all were
+// stored).  h_seq: the chunk is on the host and goes up into a->d_seq in pieces under the hashing, as in yh_sketch_dna.
+static int acc_hash(yh_sketch_acc* a, const u8* d_seq, const u8* h_seq, u64 n_bytes, u64* total) {
+    const u64 n_win = n_bytes - a->k + 1, room = a->capacity - a->n_entries;
+    u64* tail = a->key + a->n_entries;
+    YH_HIP(hipMemsetAsync(a->d_cnt, 0, sizeof(u64), a->s_comp));
+    if (!h_seq) {
+        YH_TRY(launch_sketch(d_seq, n_bytes, a->k, a->seed, a->max_hash, room, tail, a->d_cnt, a->s_comp, 0, n_win));
+    } else {
+        const u64 piece = 32ull << 20;
+        u64 done_win = 0;
+        int flip = 0;
+        for (u64 p0 = 0; p0 < n_bytes; p0 += piece, flip ^= 1) {
+            const u64 p1 = std::min<u64>(n_bytes, p0 + piece);
+            YH_HIP(hipMemcpyAsync(a->d_seq + p0, h_seq + p0, p1 - p0, hipMemcpyHostToDevice, a->s_copy));
+            YH_HIP(hipEventRecord(a->ev[flip], a->s_copy));
+            YH_HIP(hipStreamWaitEvent(a->s_comp, a->ev[flip], 0));
+            // windows whose bytes are all there, in whole workgroups (the last piece: all that is left)
+            const u64 avail = p1 >= a->k ? p1 - a->k + 1 : 0;
+            const u64 upto = (p1 == n_bytes) ? n_win : (avail / SK_WIN_ALIGN) * SK_WIN_ALIGN;
+            if (upto > done_win) {
+                YH_TRY(launch_sketch(a->d_seq, p1, a->k, a->seed, a->max_hash, room, tail, a->d_cnt, a->s_comp, done_win, upto));
+                done_win = upto;
+            }
+        }
+    }
+    YH_HIP(hipMemcpyAsync(total, a->d_cnt, sizeof(u64), hipMemcpyDeviceToHost, a->s_comp));
+    YH_HIP(hipStreamSynchronize(a->s_comp));
+    return YH_OK;
+}
+
+static int acc_add_chunk(yh_sketch_acc* a, const u8* d_seq, const u8* h_seq, u64 n_bytes) {
+    if (n_bytes < a->k) { a->n_bytes += n_bytes; return YH_OK; }
+    // a log too full for what this chunk is expected to keep is compacted first: the chunk is then hashed once
+    const u64 n_win = n_bytes - a->k + 1;
+    const double keep = ((double)a->max_hash + 1.0) / 18446744073709551616.0;
+    const u64 expect = std::min<u64>(n_win, (u64)((double)n_win * keep * 1.25) + 4096);
+    if (a->capacity - a->n_entries < expect) YH_TRY(acc_compact(a));
+    u64 total = 0;
+    YH_TRY(acc_hash(a, d_seq, h_seq, n_bytes, &total));
+    if (total > a->capacity - a->n_entries) {  // nothing of it counts: room for the reported number, then once more from HBM
+        YH_TRY(acc_make_room(a, total));
+        ++a->n_rehashed;
+        u64 again = 0;
+        YH_TRY(acc_hash(a, d_seq, nullptr, n_bytes, &again));
+        if (again != total) { yh_set_error("kept hashes changed between two passes"); return YH_ERR_HIP; }
+    }
+    a->n_entries += total;
+    a->n_kept += total;
+    a->n_bytes += n_bytes;
+    return YH_OK;
+}
+
+extern "C" int yh_sketch_acc_create(int device_id, int ksize, uint64_t seed, uint64_t max_hash, uint64_t cap_entries, yh_sketch_acc** out) {
+    if (!out) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+    *out = nullptr;
+    if (ksize < 1 || ksize > 255) { yh_set_error("ksize must be in [1, 255]"); return YH_ERR_INVALID_ARG; }
+    if (cap_entries > ACC_MAX_CAP) { yh_set_error("cap_entries must be at most %llu", ACC_MAX_CAP); return YH_ERR_INVALID_ARG; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        yh_set_error("no HIP device available (libyacht_hip has no CPU fallback)");
+        return YH_ERR_NO_DEVICE;
+    }
+    if (device_id < 0 || device_id >= ndev) { yh_set_error("device_id %d out of range", device_id); return YH_ERR_NO_DEVICE; }
+    YH_HIP(hipSetDevice(device_id));
+    yh_sketch_acc* a = new yh_sketch_acc();
+    a->device = device_id; a->k = (u32)ksize; a->seed = seed; a->max_hash = max_hash;
+    auto init = [&]() -> int {
+        YH_HIP(hipStreamCreateWithFlags(&a->s_copy, hipStreamNonBlocking));
+        YH_HIP(hipStreamCreateWithFlags(&a->s_comp, hipStreamNonBlocking));
+        YH_HIP(hipEventCreateWithFlags(&a->ev[0], hipEventDisableTiming));
+        YH_HIP(hipEventCreateWithFlags(&a->ev[1], hipEventDisableTiming));
+        YH_HIP(hipMalloc((void**)&a->d_cnt, sizeof(u64)));
+        return acc_grow(a, cap_entries ? cap_entries : ACC_DEFAULT_CAP);
+    };
+    const int rc = init();
+    if (rc != YH_OK) { (void)yh_sketch_acc_destroy(a); return rc; }
+    *out = a;
+    return YH_OK;
+}
+
+extern "C" int yh_sketch_acc_destroy(yh_sketch_acc* a) {
+    if (!a) return YH_OK;
+    if (a->device >= 0) (void)hipSetDevice(a->device);
+    if (a->s_copy) { (void)hipStreamSynchronize(a->s_copy); (void)hipStreamDestroy(a->s_copy); }
+    if (a->s_comp) { (void)hipStreamSynchronize(a->s_comp); (void)hipStreamDestroy(a->s_comp); }
+    for (hipEvent_t e : a->ev) if (e) (void)hipEventDestroy(e);
+    for (void* p : {(void*)a->key, (void*)a->cnt, (void*)a->work, a->tmp, (void*)a->d_seq, (void*)a->d_cnt}) if (p) (void)hipFree(p);
+    delete a;
+    return YH_OK;
+}
+
+extern "C" int yh_sketch_acc_add(yh_sketch_acc* a, const uint8_t* seq, uint64_t n_bytes) {
+    if (!acc_ok(a)) return YH_ERR_INVALID_ARG;
+    if (n_bytes && !seq) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+    YH_HIP(hipSetDevice(a->device));
+    if (n_bytes >= a->k && a->seq_cap < n_bytes) {
+        if (a->d_seq) (void)hipFree(a->d_seq);
+        a->d_seq = nullptr; a->seq_cap = 0;
+        YH_HIP(hipMalloc((void**)&a->d_seq, n_bytes + 64));
+        a->seq_cap = n_bytes;
+    }
+    const int rc = acc_add_chunk(a, a->d_seq, seq, n_bytes);
+    if (rc != YH_OK) { (void)hipStreamSynchronize(a->s_copy); (void)hipStreamSynchronize(a->s_comp); }  // (the caller's buffer is let go)
+    return rc;
+}
+
+extern "C" int yh_sketch_acc_add_device(yh_sketch_acc* a, const uint8_t* d_seq, uint64_t n_bytes) {
+    if (!acc_ok(a)) return YH_ERR_INVALID_ARG;
+    if (n_bytes && !d_seq) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+    YH_HIP(hipSetDevice(a->device));
+    const int rc = acc_add_chunk(a, d_seq, nullptr, n_bytes);
+    if (rc != YH_OK) (void)hipStreamSynchronize(a->s_comp);
+    return rc;
+}
+
+extern "C" int yh_sketch_acc_add_hashes(yh_sketch_acc* a, const uint64_t* hashes, const uint64_t* counts, uint64_t n) {
+    if (!acc_ok(a)) return YH_ERR_INVALID_ARG;
+    if (n && !hashes) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+    for (u64 i = 0; i < n; ++i)
+        if (hashes[i] > a->max_hash) { yh_set_error("hash %llu (entry %llu) is above max_hash %llu", (u64)hashes[i], i, a->max_hash); return YH_ERR_INVALID_ARG; }
+    if (!n) return YH_OK;
+    if (n > ACC_MAX_CAP) { yh_set_error("the accumulator holds at most %llu entries", ACC_MAX_CAP); return YH_ERR_UNSUPPORTED; }
+    YH_HIP(hipSetDevice(a->device));
+    if (a->capacity - a->n_entries < n) YH_TRY(acc_make_room(a, n));
+    hipStream_t st = a->s_comp;
+    const u64 at = a->n_entries;
+    if (a->n_filled < at) k_acc_ones<<<acc_blocks(at - a->n_filled), SG_THREADS, 0, st>>>(a->cnt + a->n_filled, at - a->n_filled);
+    if (!counts) k_acc_ones<<<acc_blocks(n), SG_THREADS, 0, st>>>(a->cnt + at, n);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(a->key + at, hashes, n * sizeof(u64), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && counts) e = hipMemcpyAsync(a->cnt + at, counts, n * sizeof(u64), hipMemcpyHostToDevice, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) { yh_set_error("adding hashes failed: %s", hipGetErrorString(e)); return YH_ERR_HIP; }
+    a->n_entries = a->n_filled = at + n;
+    a->n_kept += n;
+    return YH_OK;
+}
+
+extern "C" int yh_sketch_acc_get_info(yh_sketch_acc* a, yh_sketch_acc_info* info) {
+    if (!acc_ok(a)) return YH_ERR_INVALID_ARG;
+    if (!info) { yh_set_error("info is null"); return YH_ERR_INVALID_ARG; }
+    info->n_bytes = a->n_bytes;
+    info->n_kept = a->n_kept;
+    info->n_entries = a->n_entries;
+    info->n_compacted = a->n_compacted;
+    info->capacity = a->capacity;
+    info->n_compactions = a->n_compactions;
+    info->n_rehashed_chunks = a->n_rehashed;
+    return YH_OK;
+}
+
+extern "C" int yh_sketch_acc_finish_device(yh_sketch_acc* a, const uint64_t** d_mins, const uint64_t** d_abund, uint64_t* n) {
+    if (!acc_ok(a)) return YH_ERR_INVALID_ARG;
+    if (!d_mins || !d_abund || !n) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+    YH_HIP(hipSetDevice(a->device));
+    YH_TRY(acc_compact(a));
+    *d_mins = (const uint64_t*)a->key;
+    *d_abund = (const uint64_t*)a->cnt;
+    *n = a->n_compacted;
+    return YH_OK;
+}
+
+extern "C" int yh_sketch_acc_finish(yh_sketch_acc* a, uint64_t cap, uint64_t* mins_out, uint64_t* abund_out, uint64_t* n_out) {
+    if (!acc_ok(a)) return YH_ERR_INVALID_ARG;
+    if (!n_out || (cap && (!mins_out || !abund_out))) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+    *n_out = 0;
+    YH_HIP(hipSetDevice(a->device));
+    YH_TRY(acc_compact(a));
+    const u64 n = a->n_compacted;
+    *n_out = n;
+    if (!cap || !n) return YH_OK;
+    if (n > cap) { yh_set_error("sketch buffers hold %llu entries, %llu needed", (u64)cap, n); return YH_ERR_CAPACITY; }
+    YH_HIP(hipMemcpyAsync(mins_out, a->key, n * sizeof(u64), hipMemcpyDeviceToHost, a->s_comp));
+    YH_HIP(hipMemcpyAsync(abund_out, a->cnt, n * sizeof(u64), hipMemcpyDeviceToHost, a->s_comp));
+    YH_HIP(hipStreamSynchronize(a->s_comp));
+    return YH_OK;
 }

@@ -6,13 +6,16 @@ sketch_sample.py:31-49).  Here the k-mer hashing runs in libyacht_hip.so (yh_ske
 module does the file handling: FASTA/FASTQ (optionally gzip) in, sourmash-format signatures out
 (yacht_amd.sigio), one signature per file (all records merged) like `sourmash sketch` without
 `--singleton`.  `yacht sketch ref` sends many records or genome files through ONE device call
-(yh_sketch_segments: one segment, one finished sketch each); `yacht sketch sample` does not.
+(yh_sketch_segments: one segment, one finished sketch each); `yacht sketch sample` streams its read files, chunk by
+chunk, through ONE device accumulator (yh_sketch_acc) that keeps the distinct hashes and their counts in HBM.
 """
 from __future__ import annotations
 
 import ctypes as C
 import gzip
 import os
+import queue
+import threading
 from typing import Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -297,14 +300,239 @@ def add_sample_arguments(parser) -> None:
     parser.add_argument("--outfile", help="Output file name.", required=True)
 
 
+# ---- one sketch out of many chunks (yh_sketch_acc): what `yacht sketch sample` streams its read files through ----
+class SketchAccumulator:
+    """The distinct kept hashes of everything added so far, with their counts, held on the device (yh_sketch_acc_*).
+    A chunk is records joined by a byte that is not a base; the result depends only on the multiset of kept hashes, not
+    on the chunking or on `cap_entries` (the log's first capacity; 0: the library's default)."""
+
+    def __init__(self, ksize: int, scaled: int = 1000, seed: int = DEFAULT_SEED, device: int = 0, cap_entries: int = 0,
+                 max_hash: Optional[int] = None):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        self.max_hash = max_hash_for_scaled(scaled) if max_hash is None else int(max_hash)
+        _lib.check(self._lib.yh_sketch_acc_create(device, ksize, seed, self.max_hash, cap_entries, C.byref(self._h)))
+
+    def _handle(self) -> C.c_void_p:
+        if not self._h:
+            raise _lib.YachtHipError(_lib.YH_ERR_INVALID_ARG, "the sketch accumulator is closed")
+        return self._h
+
+    def add(self, chunk) -> None:
+        buf = chunk if isinstance(chunk, np.ndarray) else np.frombuffer(chunk, dtype=np.uint8)
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        _lib.check(self._lib.yh_sketch_acc_add(self._handle(), C.c_void_p(buf.ctypes.data) if buf.size else None, buf.size))
+
+    def add_device(self, d_ptr: int, n_bytes: int) -> None:
+        """a chunk that is already in device memory (complete when the call is made)"""
+        _lib.check(self._lib.yh_sketch_acc_add_device(self._handle(), C.c_void_p(d_ptr), n_bytes))
+
+    def add_hashes(self, hashes, counts=None) -> None:
+        h = np.ascontiguousarray(hashes, dtype=np.uint64)
+        c = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint64)
+        if c is not None and c.shape != h.shape:
+            raise ValueError("hashes and counts differ in length")
+        _lib.check(self._lib.yh_sketch_acc_add_hashes(self._handle(), C.c_void_p(h.ctypes.data) if h.size else None,
+                                                      C.c_void_p(c.ctypes.data) if c is not None and c.size else None, h.size))
+
+    def info(self) -> dict:
+        i = _lib.SketchAccInfo()
+        _lib.check(self._lib.yh_sketch_acc_get_info(self._handle(), C.byref(i)))
+        return {f: int(getattr(i, f)) for f, _t in _lib.SketchAccInfo._fields_}
+
+    def finish(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(mins strictly ascending, their summed counts), both uint64; the accumulator goes on"""
+        n = C.c_uint64(0)
+        _lib.check(self._lib.yh_sketch_acc_finish(self._handle(), 0, None, None, C.byref(n)))
+        mins = np.empty(int(n.value), dtype=np.uint64)
+        counts = np.empty(int(n.value), dtype=np.uint64)
+        if mins.size:
+            _lib.check(self._lib.yh_sketch_acc_finish(self._handle(), mins.size, C.c_void_p(mins.ctypes.data),
+                                                      C.c_void_p(counts.ctypes.data), C.byref(n)))
+        return mins, counts
+
+    def finish_device(self) -> Tuple[int, int, int]:
+        """(device address of the mins, of the counts, their number): valid until the next call on the accumulator"""
+        m, a, n = C.c_void_p(), C.c_void_p(), C.c_uint64(0)
+        _lib.check(self._lib.yh_sketch_acc_finish_device(self._handle(), C.byref(m), C.byref(a), C.byref(n)))
+        return int(m.value or 0), int(a.value or 0), int(n.value)
+
+    def close(self) -> None:
+        if self._h:
+            h, self._h = self._h, C.c_void_p()
+            self._lib.yh_sketch_acc_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+READ_BLOCK_BYTES = 8 << 20    # of file (decompressed) per read of iter_sequence_chunks
+READ_AHEAD_CHUNKS = 2         # chunks the reader thread may hold ready while the device works on one
+_ChunkQueue = queue.Queue
+
+
+def iter_sequence_chunks(path: str, budget: int, block_bytes: int = READ_BLOCK_BYTES) -> Iterator[bytes]:
+    """The sequences of read_sequences(path), in order, as buffers of WHOLE records joined by a newline, each of at most
+    `budget` bytes (a longer record goes alone) -- read in blocks, so that memory is bounded by the budget and the longest
+    record, not by the file.  What is carried from block to block is the unfinished line and, for FASTA, the lines of the
+    current record.  read_sequences' rules, which need the global line index: the first byte decides the format; FASTQ line
+    4 i + 1 is a sequence when line 4 i starts with '@' (stripped; the last line counts without a newline); FASTA lines are
+    right-stripped, blank ones skipped, and whatever precedes the first '>' is dropped."""
+    budget = max(int(budget), 1)
+    pieces: List[bytes] = []   # of the chunk being gathered: it is b"\n".join(pieces),
+    held = 0                   # this long
+
+    def take(records: List[bytes]) -> Iterator[bytes]:
+        nonlocal pieces, held
+        if not records:
+            return
+        joined = b"\n".join(records)
+        if held + len(joined) + (1 if pieces else 0) <= budget:  # (all of a block's records at once: the usual case)
+            held += len(joined) + (1 if pieces else 0)
+            pieces.append(joined)
+            return
+        for r in records:
+            if pieces and held + 1 + len(r) > budget:
+                yield b"\n".join(pieces)
+                pieces, held = [], 0
+            held += len(r) + (1 if pieces else 0)
+            pieces.append(r)
+
+    opener = gzip.open if path.endswith(".gz") else open
+    with opener(path, "rb") as f:
+        block = f.read(block_bytes)
+        if not block:
+            return
+        fastq = block[:1] == b"@"
+        carry: List[bytes] = []    # the unfinished line, in the pieces it arrived in
+        g = 0                      # global index of the next line
+        head_ok = False            # FASTQ: the last first-of-four line seen starts with '@'
+        named, parts = False, []   # FASTA: a header has been seen; the lines of the current record
+
+        def lines_in(lines: List[bytes]) -> List[bytes]:
+            """the records that these consecutive lines (the first has index g) complete"""
+            nonlocal g, head_ok, named, parts
+            recs: List[bytes] = []
+            if fastq:
+                h0, s0 = (-g) % 4, (1 - g) % 4
+                oks = [h.startswith(b"@") for h in lines[h0::4]]
+                seqs = lines[s0::4]
+                flags = ([head_ok] + oks) if s0 < h0 else oks   # (s0 < h0: the first sequence line's header came earlier)
+                if all(flags[:len(seqs)]):
+                    recs = [s.strip() for s in seqs]
+                else:
+                    recs = [s.strip() for ok, s in zip(flags, seqs) if ok]
+                if oks:
+                    head_ok = oks[-1]
+            else:
+                for line in lines:
+                    line = line.rstrip()
+                    if line.startswith(b">"):
+                        if named:
+                            recs.append(b"".join(parts))
+                        named, parts = True, []
+                    elif line:
+                        parts.append(line)
+            g += len(lines)
+            return recs
+
+        while block:
+            if b"\n" in block:
+                lines = (b"".join(carry) + block if carry else block).split(b"\n")
+                carry = [lines.pop()]
+                yield from take(lines_in(lines))
+            else:
+                carry.append(block)
+            block = f.read(block_bytes)
+        yield from take(lines_in([b"".join(carry)]))   # (the last line, with or without text)
+        if not fastq and named:
+            yield from take([b"".join(parts)])
+    if pieces:
+        yield b"\n".join(pieces)
+
+
+def read_chunks_ahead(paths: Sequence[str], budget: int) -> Iterator[bytes]:
+    """iter_sequence_chunks of every path, in order, produced by a reader thread that stays at most READ_AHEAD_CHUNKS chunks
+    ahead of the consumer (a bounded queue: file reads and gzip release the GIL, so the next chunks are read and
+    decompressed while the device hashes the current one)."""
+    q = _ChunkQueue(maxsize=READ_AHEAD_CHUNKS)
+    stop = threading.Event()
+    done = object()
+
+    def put(item) -> bool:
+        while not stop.is_set():
+            try:
+                q.put(item, timeout=0.1)
+                return True
+            except queue.Full:
+                pass
+        return False
+
+    def produce():
+        try:
+            for p in paths:
+                for chunk in iter_sequence_chunks(p, budget):
+                    if not put(chunk):
+                        return
+            put(done)
+        except BaseException as e:  # (handed to the consumer, which raises it)
+            put(e)
+
+    t = threading.Thread(target=produce, name="yacht-sketch-reader", daemon=True)
+    t.start()
+    try:
+        while True:
+            item = q.get()
+            if item is done:
+                return
+            if isinstance(item, BaseException):
+                raise item
+            yield item
+    finally:
+        stop.set()
+        t.join()
+
+
+def use_whole_sample_path() -> bool:
+    """YACHT_SKETCH_SAMPLE=whole: every file read whole, one device call, the kept hashes sorted on the host -- for A/B
+    checks against the streamed path."""
+    return os.environ.get("YACHT_SKETCH_SAMPLE", "") == "whole"
+
+
+def sketch_sample_files(paths: Sequence[str], ksize: int = 31, scaled: int = 1000, seed: int = DEFAULT_SEED, device: int = 0,
+                        budget: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """(mins ascending, abundances) of all reads of all files merged -- what sketch_sequences gives for their sequences --
+    with the files streamed in chunks of `budget` bytes (default: batch_bytes()) through ONE device accumulator: host
+    memory is bounded by the budget, the sort and the counting happen on the device."""
+    budget = batch_bytes() if budget is None else budget
+    with SketchAccumulator(ksize, scaled, seed, device) as acc:
+        for chunk in read_chunks_ahead(list(paths), budget):
+            acc.add(chunk)
+        mins, counts = acc.finish()
+    return mins, counts.astype(np.int64)
+
+
 def main_sample(args) -> None:
-    """All reads of the one or two files merged into ONE signature with abundances."""
+    """All reads of the one or two files merged into ONE signature with abundances.  The files are streamed through a device
+    accumulator (sketch_sample_files); YACHT_SKETCH_SAMPLE=whole reads them whole and makes one device call instead."""
     if len(args.infile) not in (1, 2):
         raise ValueError("Please provide either one file for single-end reads or two files for paired-end reads.")
-    seqs: List[bytes] = []
-    for path in args.infile:
-        seqs += [s for _n, s in read_sequences(path)]
-    mins, ab = sketch_sequences(seqs, args.kmer, args.scaled)
+    if use_whole_sample_path():
+        seqs: List[bytes] = []
+        for path in args.infile:
+            seqs += [s for _n, s in read_sequences(path)]
+        mins, ab = sketch_sequences(seqs, args.kmer, args.scaled)
+    else:
+        mins, ab = sketch_sample_files(args.infile, args.kmer, args.scaled)
     sig = sigio.Signature(sigio.MinHash(mins, args.kmer, max_hash_for_scaled(args.scaled), ab),
                           name=os.path.basename(args.infile[0]), filename=args.infile[0])
     sigio.write_sig_zip([sig], args.outfile)
