@@ -988,6 +988,70 @@ int yh_sketch_acc_get_info(yh_sketch_acc* acc, yh_sketch_acc_info* info);
 int yh_sketch_acc_finish(yh_sketch_acc* acc, uint64_t cap, uint64_t* mins_out, uint64_t* abund_out, uint64_t* n_out);
 int yh_sketch_acc_finish_device(yh_sketch_acc* acc, const uint64_t** d_mins, const uint64_t** d_abund, uint64_t* n);
 
+/* ---- compare: samples against samples, no database (additive to ABI 8) ----
+ * Every pass above measures a sample against the references.  This one measures two sets of samples, A and B, against each
+ * other: the integers behind Jaccard, containment, Bray-Curtis and cosine of every pair.  No yh_db is involved.
+ * Each set is laid out as every batched pass lays out a block: d_a holds the samples back to back, each strictly
+ * ascending; d_a_off[n_a + 1] their offsets; d_a_abund uint32 abundances parallel to d_a, NULL = every abundance is 1.
+ * B likewise.  Passing the SAME pointers (and sizes) for A and B is the symmetric call.
+ * Keep bytes: d_a_keep / d_b_keep run parallel to the hashes; a hash takes part iff its side's keep pointer is NULL or
+ * (keep[h] & keep_and) == keep_eq.  They are the flag bytes yh_explain* writes: keep_and = 1 << k, keep_eq = 0 selects "not
+ * explained by call set k"; keep_and = keep_eq = 0x80 selects "known to the database".
+ * For i < n_a, j < n_b and I = the kept hashes of A_i that are also kept hashes of B_j, cells[i * ld_cells + j] is
+ *   n_shared = |I|,  sum_min = sum over I of min(a_i(h), b_j(h)),  dot = sum over I of a_i(h) * b_j(h), exact in 128 bits
+ * (two abundances of 2^32 - 1 on two shared hashes pass 2^64), and one yh_compare_self row per sample of A and of B gives
+ * what the metrics divide by: its kept hashes, their abundance sum and the 128-bit sum of squares.
+ * Contract: all outputs are exact integers and do not depend on arrival order (no atomics meet anywhere: a lane owns a
+ * cell, carries come from the low words' sums); every cell of the n_a x n_b matrix (ld_cells >= n_b) and every self row is
+ * written by every call and nothing outside them; an empty sample or a mask that keeps nothing gives zero cells; in the
+ * symmetric call cell(i, j) == cell(j, i) (only the tiles with i-tile <= j-tile are computed, and mirrored) and cell(i, i)
+ * agrees with self row i.  A sample is shorter than 2^32 hashes; n_a, n_b <= YH_COMPARE_MAX_SAMPLES (a maximal call's matrix
+ * is 128 MiB), YH_ERR_INVALID_ARG beyond.
+ * How it runs: a workgroup owns a tile of YH_COMPARE_TILE x YH_COMPARE_TILE cells and one window of the hash space (equal
+ * parts of [0, the call's largest hash]; the host cuts up to YH_COMPARE_MAX_WINDOWS windows when the tiles alone do not fill
+ * the device, and a second launch sums the windows).  It stages YH_COMPARE_SLICE entries of each of the tile's samples in LDS per round and merges every
+ * cell up to the smallest last staged hash; a slice is never truncated, so any strictly ascending input is exact.  At most
+ * three launches, whatever n_a and n_b.
+ *
+ * yh_compare_work_bytes  bytes of d_work the device form needs; 0 beyond the limits
+ * yh_compare_device      everything on device buffers, enqueued on `stream` (a hipStream_t, NULL = the default stream)
+ *                        without synchronizing, nothing allocated.  total_a / total_b are the caller's copy of the last
+ *                        offsets, as in yh_explain_batch_device: they size launches only, the kernels walk the device offsets.
+ *                        Nothing is checked on the device: unsorted samples give wrong cells, never an access outside.
+ * yh_compare             the synchronous host form: checks the limits, the offsets (from 0, never descending:
+ *                        YH_ERR_INVALID_ARG) and every sample's ordering (YH_ERR_UNSORTED) BEFORE any device work, then
+ *                        uploads, runs and downloads.                                                              */
+#ifndef YH_COMPARE_TILE
+#define YH_COMPARE_TILE 8          /* samples a side of a workgroup's tile of cells */
+#endif
+#ifndef YH_COMPARE_SLICE
+#define YH_COMPARE_SLICE 256       /* entries of a sample staged in LDS per round */
+#endif
+#define YH_COMPARE_MAX_WINDOWS 64  /* a power of two: window w of n starts at w * ((largest hash >> log2 n) + 1) */
+#define YH_COMPARE_MAX_SAMPLES 2048
+typedef struct yh_compare_cell {
+    uint64_t n_shared;   /* |I|                                          */
+    uint64_t sum_min;    /* sum over I of min(a_i(h), b_j(h))            */
+    uint64_t dot_lo;     /* sum over I of a_i(h) * b_j(h), 128 bits      */
+    uint64_t dot_hi;
+} yh_compare_cell;
+typedef struct yh_compare_self {
+    uint64_t n_kept;     /* number of kept hashes                        */
+    uint64_t sum;        /* sum of their abundances                      */
+    uint64_t sq_lo;      /* sum of their squares, 128 bits               */
+    uint64_t sq_hi;
+} yh_compare_self;
+uint64_t yh_compare_work_bytes(uint64_t n_a, uint64_t n_b, uint64_t total_a, uint64_t total_b);
+int yh_compare_device(const uint64_t* d_a, const uint64_t* d_a_off, const uint32_t* d_a_abund, const uint8_t* d_a_keep,
+                      uint64_t n_a, uint64_t total_a, const uint64_t* d_b, const uint64_t* d_b_off, const uint32_t* d_b_abund,
+                      const uint8_t* d_b_keep, uint64_t n_b, uint64_t total_b, uint8_t keep_and, uint8_t keep_eq,
+                      yh_compare_cell* d_cells, uint64_t ld_cells, yh_compare_self* d_self_a, yh_compare_self* d_self_b,
+                      void* d_work, uint64_t work_bytes, void* stream);
+int yh_compare(const uint64_t* a, const uint64_t* a_off, const uint32_t* a_abund, const uint8_t* a_keep, uint64_t n_a,
+               const uint64_t* b, const uint64_t* b_off, const uint32_t* b_abund, const uint8_t* b_keep, uint64_t n_b,
+               uint8_t keep_and, uint8_t keep_eq, int device_id, yh_compare_cell* cells, uint64_t ld_cells,
+               yh_compare_self* self_a, yh_compare_self* self_b);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,10 @@ YH_GATHER_NOBODY = 0xFFFFFFFF  # an owner entry: no reference took the hash
 YH_LCA_MAX_DEPTH = 16  # deepest node of a taxonomy (yh_db_set_taxonomy)
 YH_LCA_NONE = 0xFFFFFFFF  # a node entry: no reference holds the hash
 YH_LCA_BATCH_TILE = 1024
+YH_COMPARE_TILE = 8  # samples a side of a workgroup's tile of cells (yh_compare*)
+YH_COMPARE_SLICE = 256  # entries of a sample staged in LDS per round
+YH_COMPARE_MAX_WINDOWS = 64  # windows a tile's walk over [0, the call's largest hash] is cut into at most
+YH_COMPARE_MAX_SAMPLES = 2048  # samples a side per call
 YH_LOOKUP_AUTO, YH_LOOKUP_STREAM, YH_LOOKUP_INDEXED = 0, 1, 2
 
 _ERR_NAMES = {
@@ -95,6 +99,14 @@ class Timing(C.Structure):
 class SketchAccInfo(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("n_bytes", "n_kept", "n_entries", "n_compacted", "capacity", "n_compactions",
                                           "n_rehashed_chunks")]
+
+
+class CompareCell(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_shared", "sum_min", "dot_lo", "dot_hi")]
+
+
+class CompareSelf(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_kept", "sum", "sq_lo", "sq_hi")]
 
 
 _u64p = C.POINTER(C.c_uint64)
@@ -208,6 +220,11 @@ SIGNATURES = {
     "yh_sketch_acc_get_info": (C.c_int, [_vp, C.POINTER(SketchAccInfo)]),
     "yh_sketch_acc_finish": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_uint64)]),
     "yh_sketch_acc_finish_device": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_uint64)]),
+    "yh_compare_work_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
+    "yh_compare_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint8,
+                                    C.c_uint8, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "yh_compare": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, C.c_uint8, C.c_uint8, C.c_int, _vp,
+                             C.c_uint64, _vp, _vp]),
     "yh_hyp_test": (C.c_int, [C.c_uint64, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "yh_train_select": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.POINTER(C.c_uint64)]),
     "yh_sig_batch_read": (C.c_int, [C.POINTER(C.c_char_p), C.c_uint64, C.c_int, C.POINTER(_vp)]),

@@ -1,6 +1,7 @@
 """`yacht` command line for the hot-path commands: `yacht train` and `yacht run`
 (reference src/yacht/__init__.py:54-136 dispatches the same sub-commands to the same
-add_arguments/main pairs), plus `yacht sketch ref|sample` on the HIP sketcher.  The reference's
+add_arguments/main pairs), plus `yacht sketch ref|sample` on the HIP sketcher and `yacht compare`
+(sample against sample, no database).  The reference's
 other sub-commands (download, convert) need the network / NCBI taxonomy tools and are out of this
 repository's scope.
 
@@ -12,7 +13,7 @@ from __future__ import annotations
 import argparse
 import sys
 
-from . import make_training_data_from_sketches, run_YACHT, sketch
+from . import compare, make_training_data_from_sketches, run_YACHT, sketch
 from .utils import __version__
 
 OUT_OF_SCOPE = ("download", "convert")
@@ -38,6 +39,10 @@ def build_parser() -> argparse.ArgumentParser:
     smp = sk_sub.add_parser("sample", description="Sketch a metagenomic sample")
     sketch.add_sample_arguments(smp)
     smp.set_defaults(func=sketch.main_sample)
+    cmp_ = sub.add_parser("compare", description="Compare samples with one another: k-mer similarity of every pair (no database)",
+                          formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    compare.add_arguments(cmp_)
+    cmp_.set_defaults(func=compare.main)
     for name in OUT_OF_SCOPE:
         sub.add_parser(name, add_help=False)
     return parser

@@ -516,7 +516,8 @@ def main(args, files: List[str]) -> dict:
     the wall time of the host-form yh_gather calls of samples whose tables the host recomputed, or of every sample under
     YACHT_COHORT_GATHER=loop), gpu_lca and lca_repacked_blocks (only with --lineages: device time of the block's
     yh_lca_batch_device and rows pack -- under YACHT_COHORT_LCA=loop the HOST WALL time of every sample's host-form yh_lca call,
-    not device time -- and the blocks whose rows were packed a second time into a larger buffer), d2h, assemble, writes (what the write pool had left after the last block), cohort_files (the two
+    not device time -- and the blocks whose rows were packed a second time into a larger buffer), gpu_compare (only with
+    --compare: the HOST WALL time of the host-form yh_compare calls after the blocks, uploads and downloads included), d2h, assemble, writes (what the write pool had left after the last block), cohort_files (the two
     cohort tables), total."""
     timer = {k: 0.0 for k in ("check", "db", "table", "device_setup", "parse_wait", "device_wait", "gpu_h2d", "gpu_counts",
                               "gpu_presence", "gpu_abund", "gpu_explain", "gpu_gather", "d2h", "assemble", "writes", "cohort_files", "dense_fallback_blocks", "total")}
@@ -556,6 +557,13 @@ def main(args, files: List[str]) -> dict:
     # YACHT_COHORT_EXPLAIN=host: every sample's residual by its own host-form yh_explain call, as before the batched pass
     # (A/B checks); otherwise only the samples whose tables the host recomputed below take it
     device_explain = want_residual and os.environ.get("YACHT_COHORT_EXPLAIN") != "host"
+    want_compare = bool(getattr(args, "compare", False))
+    if want_compare:  # after the blocks: the samples against one another (compare.run_files)
+        from . import compare
+
+        timer["gpu_compare"] = 0.0
+        # with --residual: per sample, 1 where the call set of --residual_coverage explains the hash (None: no overlap, nothing explained)
+        compare_keeps = [None] * len(paths) if want_residual else None
     gather_plan = None
     if getattr(args, "gather", False):
         from . import gather
@@ -688,6 +696,9 @@ def main(args, files: List[str]) -> dict:
                 row = row[row["min_coverage"] == residual_cov].iloc[0]
                 summary[-1][-2:] = [float(row["f_hashes_explained"]), float(row["f_abund_explained"])]
                 explained = (sigs[s], call_sets, flags, totals, residual_cov)
+                if want_compare:  # the bit residual.write_outputs cuts residual.sig.zip by
+                    c = [float(x) for x in user_covs].index(float(residual_cov))
+                    compare_keeps[i] = ((np.asarray(flags[c], dtype=np.uint8) >> np.uint8(c % MAX_SETS)) & np.uint8(1)).astype(np.uint8)
             if tree is not None:  # the sample's non-zero lineage counts; the write pool makes its table and its rows of the cohort's
                 if device_lca:
                     mine = l_rows[l_bounds[s]:l_bounds[s + 1]]
@@ -754,6 +765,9 @@ def main(args, files: List[str]) -> dict:
         taxonomy.cohort_frame([p[0] for p in lca_parts], [p[1] if isinstance(p[1], list) else p[1].result() for p in lca_parts]).to_csv(
             os.path.join(results_folder, taxonomy.COHORT_NAME), sep="\t", index=False)
     timer["cohort_files"] = time.perf_counter() - t0
+    if want_compare:  # (the database is released: the samples, parsed again panel by panel, have the device to themselves)
+        timer["gpu_compare"] = compare.run_files(paths, [sample_stem(p) for p in paths], meta, ksize, results_folder, args.num_threads,
+                                                 compare_keeps)
     timer["total"] = time.perf_counter() - t_all
     logger.info(f"Saved results of {len(paths)} samples to {results_folder}.")
     return timer

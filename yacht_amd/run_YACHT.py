@@ -85,6 +85,12 @@ ARGUMENTS = (
                                   "results/cohort_lca.tsv then holds, per sample, the hashes outside the database, those that resolve "
                                   "above the rank, and one row per taxon at the rank.  Ignored with one sample file."
                                   % ", ".join(("superkingdom", "phylum", "class", "order", "family", "genus", "species", "strain")))),
+    ("--compare", dict(action="store_true",
+                       help="Also compare the cohort's samples with one another (two or more sample files): "
+                            "results/cohort_compare.tsv, one row per pair with the shared hashes, Jaccard, containment, "
+                            "Bray-Curtis and cosine, and results/cohort_compare_<metric>.csv matrices as `sourmash compare --csv` "
+                            "writes them; with --residual also results/cohort_compare_residual.tsv, the same table over the hashes "
+                            "the call set of --residual_coverage does not explain.  `yacht compare` does the same without a database.")),
 )
 
 # messages the reference raises with (callers and its tests match on them)
@@ -169,6 +175,10 @@ def decompress_legacy_db(genome_dir: str, num_threads: int) -> None:
 def main(args) -> None:
     files = [args.sample_file] if isinstance(args.sample_file, str) else list(args.sample_file)
     want_residual = bool(getattr(args, "residual", False))
+    if getattr(args, "compare", False) and len(files) < 2:  # (before anything is written or any device work)
+        from . import compare
+
+        raise ValueError(compare.MSG_COMPARE_NEEDS_COHORT.format(len(files)))
     if want_residual or getattr(args, "residual_coverage", None) is not None:
         from . import residual
 
