@@ -654,7 +654,7 @@ int yh_db_destroy(yh_db* db) {
                     db->d_dh, db->d_dref, db->d_dir, db->d_bkt, db->d_cbkt, db->d_ovf_keys, db->d_ovf_vals,
                     db->d_rpo, db->d_rg, db->d_rrec, db->d_rrecx, db->d_filter, db->d_hrec, db->d_hrecx, db->d_hmult, db->d_hpo,
                     db->d_work, db->d_work_count, db->d_mask, db->d_maskbits, db->d_hit, db->d_excl_e, db->d_overlap_tmp,
-                    db->d_sample_tmp, db->d_out_tmp, db->d_flag, db->d_reps, db->batch[0].d_scratch, db->batch[1].d_scratch, db->batch[2].d_scratch, db->d_sdelta, db->d_shdr, db->d_srec,
+                    db->d_sample_tmp, db->d_out_tmp, db->d_flag, db->d_reps, db->d_hitrows, db->batch[0].d_scratch, db->batch[1].d_scratch, db->batch[2].d_scratch, db->d_sdelta, db->d_shdr, db->d_srec,
                     db->d_wg_key, db->d_ghost_src, db->d_bad_word, db->d_prank, db->d_fz_rec, db->d_fz_list, db->d_fz_list2, db->d_fz_off, db->d_fz_tab};
     for (void* p : ptrs)
         if (p) yh_dfree(db, p);

@@ -254,6 +254,15 @@ struct yh_db {
     u32* pend_red_out[3] = {nullptr, nullptr, nullptr};
     u32* pend_excl_out = nullptr;
     int pipe_last_ctx = -1;  // step context of the LAST step queued when that was a pipelined one (its subset bits: yh_run_rows_device); -1 otherwise
+    // Hit rows (yh_query.hip: HitRowsOut / HitRowsIn): how a 1024-lane lookup of the fused step hands its hits to the reducer of
+    // the next launch instead of adding them into d_reps -- 32 header words (word 0 / 1: the overflow stamps of the two sets), then
+    // [2 sets][hr_bins][hr_wgs_cap][64 words]; the sets alternate with the sample parity as the counter sets do.  Allocated on
+    // first use, grown (behind a join) by the tiles seen.  Rows are never cleared, a stamp is a generation number.
+    u32* d_hitrows = nullptr;
+    u32 hr_bins = 0, hr_wgs_cap = 0;
+    u32 hr_gen = 0;          // generation of the last hit-row step (never 0: what a fresh stamp word holds)
+    u32 pend_hr_wgs = 0;     // the pending step's lookup wrote hit rows for this many workgroups (0: it counted into d_reps only)
+    u32 pend_hr_gen = 0;     // ... under this generation
 
     // pipelined host-buffer calls
     RunSlot slots[YH_RUN_SLOTS];

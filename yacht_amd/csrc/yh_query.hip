@@ -202,9 +202,115 @@ __device__ __forceinline__ void sum_replica_rows(const u32* set, u32 R, u64 n, c
             for (int r = 0; r < RPT; ++r) acc[r] += t[r][k] & ((ok[r] && g + k < R) ? ~0u : 0u);
     }
 }
+// ---- hit rows: the hand-over from a 1024-lane lookup of the fused step to the reducer of the next launch --------------
+// The dense rows cost the launch twice: one device-scope atomic per (workgroup, reference) -- each a 64-byte request of its own,
+// executed memory-side -- and a scan of every row of every reference to find the ~300 that were hit.  A hit ROW instead belongs
+// to (counter set, bin, lookup workgroup), a bin being the 4096 consecutive references one 1024-lane reducer workgroup owns: word 0
+// is the number of entries, then the entries -- the reference's index in its bin, the count of one tile (<= U x THREADS), and
+// whether it is the count of the second set (hits on shared hashes).  The lookup sorts its LDS hit table into one staging row
+// per bin and writes count word and used prefix with plain coalesced stores; it writes a count of 0 too, so nobody ever clears a
+// row, and an entry beyond the count is whatever an earlier step left.  Bin-major ([set][bin][workgroup][HR_ROW]): a reducer
+// workgroup's input is one contiguous span, which it adds into an LDS histogram.  A hit that bypassed a crowded hit table is an
+// entry of its own.  What does not fit a row goes to the dense rows as before, and the workgroup stamps the set's overflow
+// word with the step's generation: only then does the reducer also sum and clear the dense rows, which so stay zero at rest.
+// ONE stamped workgroup costs the step the whole dense scan, so a row must hold what a tile of a real sample finds in a bin:
+// 10^6-hash sample, 285 hit references of 85 205, up to 26 of them in one bin -- rows of 31 entries overflowed in every step
+// (29.9 us per step against 30.3 for the dense hand-over), rows of 63 did not (29.2).  Only the used 64-byte sectors of a row
+// are written, and the reducer reads the first sector of every row and the others where the count says so.
+// (The L2 requests and atomics per launch, before and after: profiles/fused_hitrows/.)
+constexpr u32 HR_BIN_BITS = 12, HR_BIN = 1u << HR_BIN_BITS;  // references per bin = RPT x blockDim of the 1024-lane reducer
+constexpr u32 HR_MAX_BINS = 32;                              // more references: the dense hand-over
+#ifndef YH_HR_SECTORS
+#define YH_HR_SECTORS 4
+#endif
+constexpr u32 HR_SECTOR = 16, HR_ROW = YH_HR_SECTORS * HR_SECTOR;  // words per row: four 64-byte sectors, 63 entries; only the used ones move
+static_assert(YH_HR_SECTORS >= 1 && YH_HR_SECTORS <= 4, "the reducer reads a row's first sector, then up to three more");
+constexpr u32 HR_CNT_BITS = 12, HR_SECOND = 1u << (HR_BIN_BITS + HR_CNT_BITS);
+constexpr u32 HR_HEADER = 32;                                // words in front of the rows (the two overflow stamps)
+constexpr u32 HR_MAX_WGS = 2048;                             // lookup workgroups per step at most: above, the dense hand-over
+static_assert(2u * 1024u < (1u << HR_CNT_BITS), "an entry's count: U x THREADS of the largest fused 1024-lane tile");
+static_assert(HR_BIN_BITS + HR_CNT_BITS + 1 <= 32, "index, count and set bit share a word");
+struct HitRowsOut {   // the lookup role's side (rows == null: the dense hand-over)
+    u32* rows;        // this step's set
+    u32 wg_cap;       // rows per bin
+    u32 ents;         // entries a row takes (HR_ROW - 1; YH_HITROW_ENTS: tests force a small number)
+    u32 bins;
+    u32* ovf;         // the set's overflow stamp
+    u32 gen;
+};
+struct HitRowsIn {    // the reducer role's side, of the PENDING step (rows == null: it counted into the dense rows only)
+    const u32* rows;
+    u32 wg_cap;
+    u32 wgs;          // lookup workgroups of that step: rows beyond hold older steps' data
+    const u32* ovf;
+    u32 gen;
+};
+#ifndef YH_HR_G
+#define YH_HR_G 2
+#endif
+constexpr int HR_G = YH_HR_G;  // trips of first-sector reads in flight together: two cover the 489 rows of a 10^6-hash sample's bin
+// The counts of this workgroup's RPT x blockDim references from the rows of their bin, as a histogram in LDS: hist[i] the first
+// set's of the block's i-th reference, hist[RPT x blockDim + i] the second set's.  (They stay there until the role needs them:
+// held in registers across the dense rows' reads they spilled.)  The workgroup's block lies inside ONE bin (its size divides
+// HR_BIN); entries of the bin's other references are skipped.
 template <int RPT>
+__device__ __forceinline__ void sum_hit_rows(u32 blk, u32* hist, const HitRowsIn& hr) {
+    const u32 RB = (u32)RPT * blockDim.x;
+    const u32 first = blk * RB, bin = first >> HR_BIN_BITS, lo = first & (HR_BIN - 1u);
+    for (u32 k = threadIdx.x; k < 2u * RB; k += blockDim.x) hist[k] = 0;
+    __syncthreads();
+    // The first sector of every row -- the count word and 15 entries -- four lanes per row (16 bytes each), blockDim / 4 rows per
+    // trip, HR_G trips requested before any is looked at; a row's further sectors only where its count says they are used (a
+    // second, dependent trip, taken by the rows of more than 15 entries).
+    const uint4* __restrict__ base = reinterpret_cast<const uint4*>(hr.rows + (u64)bin * hr.wg_cap * HR_ROW);
+    const u32 rpt = blockDim.x >> 2, sub = threadIdx.x & 3u, lane = threadIdx.x & 63u;
+#pragma unroll 1
+    for (u32 g = 0; g < hr.wgs; g += (u32)HR_G * rpt) {
+        u32 vx[HR_G], vy[HR_G], vz[HR_G], vw[HR_G];
+#pragma unroll
+        for (int k = 0; k < HR_G; ++k) {
+            const u32 row = min(g + (u32)k * rpt + (threadIdx.x >> 2), hr.wgs - 1u);
+            const uint4 v = base[(u64)row * (HR_ROW / 4u) + sub];
+            vx[k] = v.x; vy[k] = v.y; vz[k] = v.z; vw[k] = v.w;
+        }
+#pragma unroll
+        for (int k = 0; k < HR_G; ++k) asm volatile("" : "+v"(vx[k]), "+v"(vy[k]), "+v"(vz[k]), "+v"(vw[k]));
+#pragma unroll
+        for (int k = 0; k < HR_G; ++k) {
+            const u32 row = g + (u32)k * rpt + (threadIdx.x >> 2);
+            u32 cnt = min((u32)__shfl((int)vx[k], (int)(lane & ~3u)), HR_ROW - 1u);  // (word 0 of the row: its first lane's)
+            if (row >= hr.wgs) cnt = 0;
+            const auto take = [&](u32 w, u32 at) {
+                const u32 idx = (w & (HR_BIN - 1u)) - lo;
+                if (at >= 1u && at <= cnt && idx < RB)
+                    atomicAdd(&hist[((w & HR_SECOND) ? RB : 0u) + idx], (w >> HR_BIN_BITS) & ((1u << HR_CNT_BITS) - 1u));
+            };
+            take(vx[k], sub * 4u);
+            take(vy[k], sub * 4u + 1u);
+            take(vz[k], sub * 4u + 2u);
+            take(vw[k], sub * 4u + 3u);
+            if (cnt >= HR_SECTOR) {  // (cnt > 0: the row exists)
+                const uint4* more = base + (u64)row * (HR_ROW / 4u) + sub;
+                const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+                const uint4 e1 = more[HR_SECTOR / 4u];
+                const uint4 e2 = cnt >= 2u * HR_SECTOR ? more[2u * HR_SECTOR / 4u] : zero;
+                const uint4 e3 = cnt >= 3u * HR_SECTOR ? more[3u * HR_SECTOR / 4u] : zero;
+                take(e1.x, HR_SECTOR + sub * 4u); take(e1.y, HR_SECTOR + sub * 4u + 1u);
+                take(e1.z, HR_SECTOR + sub * 4u + 2u); take(e1.w, HR_SECTOR + sub * 4u + 3u);
+                take(e2.x, 2u * HR_SECTOR + sub * 4u); take(e2.y, 2u * HR_SECTOR + sub * 4u + 1u);
+                take(e2.z, 2u * HR_SECTOR + sub * 4u + 2u); take(e2.w, 2u * HR_SECTOR + sub * 4u + 3u);
+                take(e3.x, 3u * HR_SECTOR + sub * 4u); take(e3.y, 3u * HR_SECTOR + sub * 4u + 1u);
+                take(e3.z, 3u * HR_SECTOR + sub * 4u + 2u); take(e3.w, 3u * HR_SECTOR + sub * 4u + 3u);
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// (HR: the pending step handed its hits over as hit rows -- lds then holds the histogram behind its first 32 words)
+template <int RPT, bool HR = false>
 __device__ __forceinline__ void reduce_replicas_multi(u32 blk, u32* lds, u32* __restrict__ reps, u32 R, u64 n, u32* __restrict__ out,
-                                                      u32* __restrict__ maskbits, const FusedRun& f) {
+                                                      u32* __restrict__ maskbits, const FusedRun& f, const HitRowsIn& hr = HitRowsIn{}) {
     const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
     // The launch is bound by the rate of its L2 requests (the lookups' 1.27 x 10^6 isolated reads), so every request of
     // this role is paid for in full -- a timing-only build without the role: 1.2 us of the step at four rows and 1.4 at eight
@@ -227,8 +333,22 @@ __device__ __forceinline__ void reduce_replicas_multi(u32 blk, u32* lds, u32* __
         off[r] = jj[r] * 4u;  // (fits: yh_q_step_fused_ok)
         acc[r] = acc2[r] = size_j[r] = nsh[r] = rpo0[r] = rpo1[r] = 0;
     }
-    if (R >= 8u) sum_replica_rows<RPT, 8>(reps, R, n, off, ok, acc);
-    else sum_replica_rows<RPT, 4>(reps, R, n, off, ok, acc);
+    // (hit rows: the dense rows hold something only when a lookup workgroup of the step stamped the set's overflow word)
+    bool dense = true;
+    u32* const hist = lds + 32;
+    if (HR) {
+        dense = *hr.ovf == hr.gen;  // (workgroup-uniform; requested in front of the rows)
+        sum_hit_rows<RPT>(blk, hist, hr);
+    }
+    if (dense) {
+        if (R >= 8u) sum_replica_rows<RPT, 8>(reps, R, n, off, ok, acc);
+        else sum_replica_rows<RPT, 4>(reps, R, n, off, ok, acc);
+    }
+    if (HR) {
+#pragma unroll
+        for (int r = 0; r < RPT; ++r)
+            if (ok[r]) acc[r] += hist[(u32)r * blockDim.x + threadIdx.x];
+    }
     // (a wave with a hit holds one or two as a rule: one reference at a time, its reads -- eight rows, sizes, record offsets -- together)
 #pragma unroll
     for (int r = 0; r < RPT; ++r) {
@@ -240,11 +360,14 @@ __device__ __forceinline__ void reduce_replicas_multi(u32 blk, u32* lds, u32* __
             nsh[r] = f.nshared[jj[r]];
             rpo0[r] = f.work ? f.rpo[jj[r]] : 0u;
             rpo1[r] = f.work ? f.rpo[jj[r] + 1u] : 0u;
-            sum_replica_rows<1, 8>(f.reps2, R, n, off1, ok1, a2);
-            acc2[r] = a2[0];
-            for (u32 k = 0; k < R; ++k) (reps + (u64)k * n)[jj[r]] = 0;
-            if (acc2[r])
-                for (u32 k = 0; k < R; ++k) (f.reps2 + (u64)k * n)[jj[r]] = 0;
+            if (HR) acc2[r] = hist[(u32)RPT * blockDim.x + (u32)r * blockDim.x + threadIdx.x];
+            if (dense) {
+                sum_replica_rows<1, 8>(f.reps2, R, n, off1, ok1, a2);
+                acc2[r] += a2[0];
+                for (u32 k = 0; k < R; ++k) (reps + (u64)k * n)[jj[r]] = 0;
+                if (a2[0])
+                    for (u32 k = 0; k < R; ++k) (f.reps2 + (u64)k * n)[jj[r]] = 0;
+            }
         }
     }
 #pragma unroll
@@ -905,9 +1028,13 @@ struct TileLookup {
     u32 bad_gen;
 };
 // (body: `wg` = the workgroup's index among the looking-up ones; tkey / tcnt / tcnt2: 2^TBITS words of LDS each)
+// hr non-null with rows (the fused step's 1024-lane geometries only): the hit table leaves as hit rows, staged per bin in
+// `stage` (HR_MAX_BINS x HR_ROW words of LDS, word 0 of a staging row = the entries claimed) -- see HitRowsOut.
 template <int U, int THREADS, int TBITS>
-__device__ __forceinline__ void lookup_tile_body(u32 wg, u32* tkey, u32* tcnt, u32* tcnt2, const TileLookup& q) {
+__device__ __forceinline__ void lookup_tile_body(u32 wg, u32* tkey, u32* tcnt, u32* tcnt2, const TileLookup& q,
+                                                 const HitRowsOut* hr = nullptr, u32* stage = nullptr) {
     constexpr u32 TSLOTS = 1u << TBITS;
+    const bool rows_out = hr && hr->rows;  // (workgroup-uniform: a kernel argument)
     const u64* __restrict__ sample = q.sample;
     const u64 n = q.n;
     const YhDirView& dv = q.dv;
@@ -929,16 +1056,30 @@ __device__ __forceinline__ void lookup_tile_body(u32 wg, u32* tkey, u32* tcnt, u
     // with a dependent round trip -- profiles/r05/ablate_step.txt: 0.2 us of the step)
     if (q.bad && *q.bad == q.bad_gen) return;
     for (u32 k = threadIdx.x; k < TSLOTS; k += THREADS) { tkey[k] = 0; tcnt[k] = 0; tcnt2[k] = 0; }
+    if (rows_out && threadIdx.x < HR_MAX_BINS) stage[threadIdx.x * HR_ROW] = 0;
     YhProbe<U> probe;
     u32 r[U];
     yh_probe_filter<U>(dv, filter, q.filter_mul, h, ok);
     yh_probe_request<U>(dv, h, ok, probe);
     __syncthreads();  // the table is clear
+    // hit rows: `cnt` hits of `ref` claim a place in the staging row of its bin; a full row: the dense rows, and the stamp
+    // that makes the reducer sum them too
+    auto put = [&](u32 ref, u32 cnt, u32 second, u32* dense) {
+        u32* const srow = stage + (ref >> HR_BIN_BITS) * HR_ROW;
+        const u32 at = atomicAdd(&srow[0], 1u);
+        if (at < hr->ents) srow[1u + at] = (ref & (HR_BIN - 1u)) | (cnt << HR_BIN_BITS) | second;
+        else { count_add(&dense[ref], cnt); *hr->ovf = hr->gen; }
+    };
     auto add = [&](u32 ref, bool shared) {
         const int slot = yh_hit_slot<TBITS>(tkey, ref);
         if (slot >= 0) {
             atomicAdd(&tcnt[slot], 1u);
             if (shared && my2) atomicAdd(&tcnt2[slot], 1u);
+            return;
+        }
+        if (rows_out) {  // crowded table: an entry of its own for this one hit (a tile of a 10^6-hash sample has a dozen such)
+            put(ref, 1u, 0u, my);
+            if (shared) put(ref, 1u, HR_SECOND, my2);
             return;
         }
         count_add(&my[ref], 1u);  // crowded table: count directly
@@ -957,11 +1098,27 @@ __device__ __forceinline__ void lookup_tile_body(u32 wg, u32* tkey, u32* tcnt, u
         }
     }
     __syncthreads();
+    if (!rows_out) {
+        for (u32 k = threadIdx.x; k < TSLOTS; k += THREADS)
+            if (tkey[k]) {
+                count_add(&my[tkey[k] - 1], tcnt[k]);
+                if (my2 && tcnt2[k]) count_add(&my2[tkey[k] - 1], tcnt2[k]);
+            }
+        return;
+    }
+    // every occupied slot claims a place in its bin's staging row, one for each set it counted in
     for (u32 k = threadIdx.x; k < TSLOTS; k += THREADS)
         if (tkey[k]) {
-            count_add(&my[tkey[k] - 1], tcnt[k]);
-            if (my2 && tcnt2[k]) count_add(&my2[tkey[k] - 1], tcnt2[k]);
+            put(tkey[k] - 1u, tcnt[k], 0u, my);
+            if (tcnt2[k]) put(tkey[k] - 1u, tcnt2[k], HR_SECOND, my2);
         }
+    __syncthreads();  // (uniform: rows_out is a kernel argument, and the verdict return above is not taken in the fused step)
+    // count word and used prefix of every bin: consecutive lanes store one contiguous span of a row
+    for (u32 i = threadIdx.x; i < hr->bins * HR_ROW; i += THREADS) {
+        const u32 bin = i / HR_ROW, w = i % HR_ROW;
+        const u32 cnt = min(stage[bin * HR_ROW], hr->ents);
+        if (w <= cnt) hr->rows[((u64)bin * hr->wg_cap + wg) * HR_ROW + w] = w ? stage[i] : cnt;
+    }
 }
 
 template <int U, int THREADS, int TBITS>
@@ -1161,6 +1318,8 @@ struct StepFused {
     TileLookup look;   u32 look_wgs;
     u32* r_reps; u32 r_R; u64 r_n; u32* r_out; u32* r_maskbits; FusedRun r_fused; u32 red_wgs;
     ExclPieces excl;   u32 excl_wgs; u32 excl_lds;  // excl_lds: the subset bits fit the launch's LDS
+    HitRowsOut hr_out;  // rows != null: this launch's lookup (a 1024-lane geometry) leaves hit rows
+    HitRowsIn hr_in;    // rows != null: the pending step left hit rows -- whatever the geometry of this launch
 };
 // (8 waves per SIMD = two workgroups per CU, as the stand-alone lookup has: 64 VGPRs; the exclusive role unrolls by 2.)
 // Dispatch order = block order: the exclusive role's workgroups come first (most of them find nothing beyond the work
@@ -1172,7 +1331,8 @@ struct StepFused {
 // job -- the pass then starts when the lookups end instead of beside them: 49.8 us per launch against 33; and claiming
 // records from a shared cursor, which hung the device on a non-uniform early exit before a barrier.)
 template <int U, int THREADS, int TBITS>
-__global__ void __launch_bounds__(THREADS, THREADS == 1024 ? 8 : 4) k_step_fused(const StepFused s) {
+// (8 for the 256-lane geometry too: left at 4 its reducer of hit rows took 67 VGPRs and the occupancy of the launch fell to 7)
+__global__ void __launch_bounds__(THREADS, 8) k_step_fused(const StepFused s) {
     extern __shared__ u32 smem[];
     constexpr u32 TSLOTS = 1u << TBITS;
     u32 b = blockIdx.x;
@@ -1185,11 +1345,13 @@ __global__ void __launch_bounds__(THREADS, THREADS == 1024 ? 8 : 4) k_step_fused
     if (b < s.red_wgs) {
         // (one block of 4 x THREADS references per workgroup: yh_q_step_fused sizes the role so; a loop over blocks here made
         // the compiler carry the lane predicates of the scan across it in registers the reads need)
-        reduce_replicas_multi<4>(b, smem, s.r_reps, s.r_R, s.r_n, s.r_out, s.r_maskbits, s.r_fused);
+        if (s.hr_in.rows) reduce_replicas_multi<4, true>(b, smem, s.r_reps, s.r_R, s.r_n, s.r_out, s.r_maskbits, s.r_fused, s.hr_in);
+        else reduce_replicas_multi<4>(b, smem, s.r_reps, s.r_R, s.r_n, s.r_out, s.r_maskbits, s.r_fused);
         return;
     }
     b -= s.red_wgs;
-    lookup_tile_body<U, THREADS, TBITS>(b, smem, smem + TSLOTS, smem + 2 * TSLOTS, s.look);
+    if (THREADS == 1024) lookup_tile_body<U, THREADS, TBITS>(b, smem, smem + TSLOTS, smem + 2 * TSLOTS, s.look, &s.hr_out, smem + 3 * TSLOTS);
+    else lookup_tile_body<U, THREADS, TBITS>(b, smem, smem + TSLOTS, smem + 2 * TSLOTS, s.look);
 }
 
 // e_j = (hashes of j that no other reference of the whole database has) + ex_e[j]
@@ -1506,8 +1668,33 @@ int yh_q_step_fused(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_overlap
     const u32 r_want = std::min<u32>(reps_env ? reps_env : fused_reps[shape.form], (u32)FUSED_MAX_REPS);
     while (R > 1 && R > r_want) R >>= 1;
     const u32 threads = shape.threads, waves = threads / 64, tslots = 1u << shape.tbits;
+    // Hit rows (HitRowsOut): the hand-over of the 1024-lane lookups while the references fit HR_MAX_BINS bins and the tiles the
+    // rows.  The rows are allocated on first use and grown by the tiles seen; growing waits for the pipeline to drain, so a
+    // pending step's rows are always in the allocation its reducer is given.  YH_NO_HITROWS / YH_HITROW_ENTS (debug tuning):
+    // tests force the dense hand-over, and a row of a few entries so that small databases overflow it.
+    static const bool hr_off = yh_tune_flag("YH_NO_HITROWS");
+    static const u32 hr_ents = (u32)std::min<long long>(std::max<long long>(yh_tune_int("YH_HITROW_ENTS", HR_ROW - 1), 1), HR_ROW - 1);
+    const u32 hr_bins = (u32)((N + HR_BIN - 1) / HR_BIN);
+    const u32 tiles = d_sample ? shape.tiles(n_sample) : 0u;
+    const bool rows_out = d_sample && threads == 1024 && !hr_off && N <= (u64)HR_MAX_BINS * HR_BIN && tiles <= HR_MAX_WGS;
+    if (rows_out && tiles > db->hr_wgs_cap) {
+        if (db->d_hitrows) {
+            while (db->pend_red >= 0 || db->pend_excl >= 0) YH_TRY(yh_q_step_fused(db, nullptr, 0, nullptr, nullptr, nullptr));
+            YH_HIP(hipStreamSynchronize(st));
+            yh_dfree(db, db->d_hitrows);
+            db->d_hitrows = nullptr;
+            db->hr_wgs_cap = 0;
+        }
+        const u32 cap = std::min<u32>(std::max<u32>((tiles + 255u) & ~255u, 512u), HR_MAX_WGS);
+        YH_HIP(hipMalloc((void**)&db->d_hitrows, ((u64)HR_HEADER + 2ull * hr_bins * cap * HR_ROW) * sizeof(u32)));
+        YH_HIP(hipMemsetAsync(db->d_hitrows, 0, HR_HEADER * sizeof(u32), st));  // (the stamps; rows are written before they are read)
+        db->hr_bins = hr_bins;
+        db->hr_wgs_cap = cap;
+    }
+    const auto hr_set = [&](u32 set) { return db->d_hitrows + HR_HEADER + (u64)set * db->hr_bins * db->hr_wgs_cap * HR_ROW; };
     StepFused s{};
     u32 lds_words = 3 * tslots;  // the lookup role's hit table
+    if (rows_out) lds_words += HR_MAX_BINS * HR_ROW;  // ... and its staging rows
     if (db->pend_excl >= 0) {   // exclusive pass of the step reduced by the previous launch
         const int c = db->pend_excl;
         s.excl = excl_args(db, db->ctx_count[c], db->ctx_work[c], db->ctx_bits[c], nullptr, db->pend_excl_out, nullptr, nullptr, true);
@@ -1533,6 +1720,11 @@ int yh_q_step_fused(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_overlap
         s.r_fused = FusedRun{reps1 + db->reps_cap, db->d_sizes, db->d_nshared, db->pend_red_out[1], db->pend_red_out[2], nullptr,
                              db->d_hpo, db->ctx_work[c], db->ctx_count[c], (u32)N};
         s.red_wgs = (u32)((N + 4ull * threads - 1) / (4ull * threads));  // (4 references per thread, ONE block per workgroup: the role does not loop)
+        if (db->pend_hr_wgs) {  // (its lookup left hit rows: the histogram of a workgroup's 4 x threads references, both sets)
+            const u32 set = (u32)db->pend_red_parity & 1u;
+            s.hr_in = HitRowsIn{hr_set(set), db->hr_wgs_cap, db->pend_hr_wgs, db->d_hitrows + set, db->pend_hr_gen};
+            lds_words = std::max(lds_words, 32u + 2u * 4u * threads);
+        }
     }
     int c_new = -1;
     if (d_sample) {
@@ -1541,7 +1733,11 @@ int yh_q_step_fused(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_overlap
         u32* const reps1 = db->d_reps + (u64)parity * 2 * db->reps_cap;
         s.look = TileLookup{d_sample, n_sample, yh_dir_view(db), shape.filter ? yh_filter_of(db) : nullptr, db->filter_mul, db->d_po, db->d_pr,
                             reps1, R - 1, N, nullptr, reps1 + db->reps_cap, db->ctx_count[c_new], nullptr, 0u};
-        s.look_wgs = shape.tiles(n_sample);
+        s.look_wgs = tiles;
+        if (rows_out) {
+            if (++db->hr_gen == 0) ++db->hr_gen;
+            s.hr_out = HitRowsOut{hr_set((u32)parity), db->hr_wgs_cap, hr_ents, db->hr_bins, db->d_hitrows + parity, db->hr_gen};
+        }
     }
     const u32 total = s.excl_wgs + s.red_wgs + s.look_wgs;
     if (total) {
@@ -1558,6 +1754,8 @@ int yh_q_step_fused(yh_db* db, const u64* d_sample, u64 n_sample, u32* d_overlap
     db->pend_excl = db->pend_red;
     db->pend_excl_out = db->pend_red >= 0 ? db->pend_red_out[1] : nullptr;
     db->pend_red = c_new;
+    db->pend_hr_wgs = rows_out ? tiles : 0u;
+    db->pend_hr_gen = db->hr_gen;
     if (d_sample) {
         db->pend_red_parity = (int)((db->pipe_k & 1) | (R << 1));
         db->pend_red_out[0] = d_overlap;
