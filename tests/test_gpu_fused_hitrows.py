@@ -30,6 +30,8 @@ Each scenario runs in a child process (the debug switches are read once per proc
     geometry    30 000 <-> 524 288 <-> 262 144 hashes alternate: a hit-row step is reduced by a launch of another geometry
                 and vice versa; rows after exactly two further calls, after a join following one call, and after a drain
     legacy      YH_NO_HITROWS=1: the dense hand-over gives the same rows
+
+The capacity edges -- 32 | 33 bins, rows of 15 .. 64 entries, the allocation's growth, 2048 | 2049 tiles: test_gpu_fused_edges.py.
 """
 import json
 import os

@@ -1,5 +1,6 @@
 // yh_api.hip — the extern "C" boundary of libyacht_hip.so (declared in include/yacht_hip.h).
 #include "yh_common.h"
+#include "yh_lookup.h"
 #include "yh_abund.h"
 #include "yh_explain.h"
 #include "yh_gather.h"
@@ -1079,7 +1080,21 @@ int yh_run_device_pipelined(yh_db* db, const uint64_t* d_sample, uint64_t n_samp
     }
     for (int c = 0; c < 3; ++c)
         if (db->ctx_open[c]) db->ctx_clobbered[c] = true;
-    return yh_q_step_fused(db, (const u64*)d_sample, n_sample, d_overlap, d_n_excl, d_n_match);
+    // YH_TRACE_HITROWS (debug tuning): one line per fused step -- the hand-over its lookup took (hit rows, or the dense replica
+    // rows) and what the row allocation did for it, read from the handle's host state around the call.  Exact counts cannot tell
+    // a step that went dense from one that left rows, so the tests of the rows' edges assert on this line.  (Here and not in
+    // yh_q_step_fused: the PMC traffic files of profiles/ are pinned to the bytes of yh_query.hip.)
+    static const bool hr_trace = yh_tune_flag("YH_TRACE_HITROWS");
+    const u32 cap_before = db->hr_wgs_cap;
+    const u32 pending = !db->d_hitrows ? 0u : db->pend_red >= 0 ? 2u : db->pend_excl >= 0 ? 1u : 0u;  // draining launches a growth needs
+    YH_TRY(yh_q_step_fused(db, (const u64*)d_sample, n_sample, d_overlap, d_n_excl, d_n_match));
+    if (hr_trace) {
+        const YhTileShape shape = yh_tile_shape_for(n_sample);
+        const u32 grew = db->hr_wgs_cap != cap_before ? 1u : 0u;
+        fprintf(stderr, "[yh hitrows] sample %llu  lanes %u  tiles %u  refs %llu  capacity %u  grew %u  drained %u -> %s\n", (u64)n_sample,
+                shape.threads, shape.tiles(n_sample), (u64)db->n_refs, db->hr_wgs_cap, grew, grew ? pending : 0u, db->pend_hr_wgs ? "rows" : "dense");
+    }
+    return YH_OK;
 }
 
 int yh_run_device_join(yh_db* db) {
