@@ -1052,6 +1052,75 @@ int yh_compare(const uint64_t* a, const uint64_t* a_off, const uint32_t* a_abund
                uint8_t keep_and, uint8_t keep_eq, int device_id, yh_compare_cell* cells, uint64_t ld_cells,
                yh_compare_self* self_a, yh_compare_self* self_b);
 
+/* ---- compare, the sparse route: the same matrix through the hashes that are shared (additive to ABI 8) ----
+ * The dense pass above costs |A_i| + |B_j| merge steps a cell whatever the pair shares.  This is a second exact way to the
+ * same yh_compare_cell / yh_compare_self values, whose time follows what the samples have in common: every kept entry of
+ * the call becomes a record (key = its hash, value = a 32-bit entry id: A's entries numbered first, B's behind them; in the
+ * symmetric call A's entries once), rocprim::radix_sort_pairs groups the records by hash over bits [0, hash_bits), and
+ * a hash held by c samples updates c (c - 1) / 2 cells (c_a * c_b in the rectangular call); a hash with one holder costs
+ * nothing more.  hash_bits (1 .. 64) is the caller's promise that every hash is below 2^hash_bits; 64 is always correct.
+ * No hash value is a sentinel: 0 and 2^64 - 1 are ordinary inputs.  An entry whose keep test fails is marked in its value
+ * and squeezed out behind the sort, so it joins no run.
+ * Contract: the written region is that of yh_compare_device -- every cell of the n_a x n_b matrix and every self row, nothing
+ * behind column n_b of a row, nothing else -- and so are the NULL / limit / ld_cells checks.  The cells are zeroed and then
+ * summed with 64-bit integer atomics (the add to dot_lo that wraps adds 1 to dot_hi): exact, independent of arrival order,
+ * and two identical calls give identical bytes.  In the symmetric call only cells i < j are summed; a last pass mirrors
+ * them and sets cell (i, i) from self row i.  The route takes total_a + total_b < 2^31 entries, YH_ERR_INVALID_ARG beyond.
+ * How it runs: the sorted records are cut into chunks of YH_COMPARE_SPARSE_CHUNK, one workgroup each, which list the runs
+ * of equal hashes that give a pair (a run that crosses a chunk edge belongs, whole, to the chunk it starts in; no run is
+ * longer than n_a + n_b entries).  Runs of up to YH_COMPARE_RUN_SMALL entries are flattened -- the lanes of a wave take
+ * consecutive pairs of consecutive runs --, a longer run gets a workgroup that stages it in LDS.
+ *
+ * yh_compare_sparse_work_bytes  bytes of d_work yh_compare_sparse_device needs; 0 beyond the limits (2^31 entries included)
+ *                               or where no device can be asked for the sort's temporary size
+ * yh_compare_sparse_device      always the sparse route, on device buffers, enqueued on `stream` without synchronizing,
+ *                               nothing allocated.  d_info (device memory, may be NULL) receives the call's figures.
+ * yh_compare_sparse_count_device the grouping alone -- records, sort, runs; no matrix, no self rows -- and its figures in
+ *                               d_info (required): the pairs a call would update, before any is made.  Route auto runs
+ *                               exactly this on the samples' prefixes; scripts/bench_compare_sparse.py times it that way.
+ * yh_compare_routed             the host form with a route: makes the checks of yh_compare BEFORE any device work (and
+ *                               `route` outside 0 .. 2 is YH_ERR_INVALID_ARG), derives hash_bits from the samples' last
+ *                               hashes, uploads, runs the route and downloads.  info may be NULL.
+ *   YH_COMPARE_ROUTE_AUTO chooses per call by a cost model, c0 + c1 * T + c2 * P < d0 + d1 * D with T the entries, P the
+ *   cell updates and D = dense_steps, its constants measured on one MI355X.  It does not sort everything to learn P: it groups
+ *   only each sample's prefix below 2^(hash_bits - YH_COMPARE_SAMPLE_LOG2) -- contiguous, because samples ascend -- with
+ *   the same code, reads the exact pair count of that window back (pairs_sampled, 8 bytes) and scales it by
+ *   2^YH_COMPARE_SAMPLE_LOG2.  FracMinHash hashes are uniform, so the window is a fair sample; an adversarial input costs
+ *   time, never correctness.  With hash_bits <= YH_COMPARE_SAMPLE_LOG2 the window is everything and estimated = 0.
+ *   Calls of 2^31 entries or more take the dense route.                                                              */
+#define YH_COMPARE_RUN_SMALL 32        /* runs of up to this many entries are flattened, longer ones get a workgroup */
+#define YH_COMPARE_SPARSE_CHUNK 2048   /* sorted records a workgroup of the runs kernel takes */
+#define YH_COMPARE_SAMPLE_LOG2 6       /* AUTO groups the hashes below 2^(hash_bits - 6): a 64th of the hash space */
+#define YH_COMPARE_ROUTE_DENSE  0
+#define YH_COMPARE_ROUTE_SPARSE 1
+#define YH_COMPARE_ROUTE_AUTO   2
+typedef struct yh_compare_sparse_info {
+    uint64_t n_entries;       /* entries that took part (kept); 0 when the dense route ran                    */
+    uint64_t n_shared_hashes; /* runs that gave at least one pair                                              */
+    uint64_t n_pair_updates;  /* P: cell updates made (exact; 0 when the dense route ran)                      */
+    uint64_t longest_run;     /* the most entries of a run that gave a pair                                    */
+    uint64_t dense_steps;     /* D: sum over the cells the dense route computes of |A_i| + |B_j|: n_b * total_a +
+                                 n_a * total_b, (n_a + 1) * total_a in the symmetric call (the cells i <= j)   */
+    uint64_t pairs_sampled;   /* auto only: exact P over the hashes below 2^(hash_bits - YH_COMPARE_SAMPLE_LOG2) */
+    uint32_t route;           /* the route that filled the matrix: DENSE or SPARSE                             */
+    uint32_t estimated;       /* 1 when the choice came from pairs_sampled scaled up                           */
+} yh_compare_sparse_info;
+uint64_t yh_compare_sparse_work_bytes(uint64_t n_a, uint64_t n_b, uint64_t total_a, uint64_t total_b);
+int yh_compare_sparse_device(const uint64_t* d_a, const uint64_t* d_a_off, const uint32_t* d_a_abund, const uint8_t* d_a_keep,
+                             uint64_t n_a, uint64_t total_a, const uint64_t* d_b, const uint64_t* d_b_off,
+                             const uint32_t* d_b_abund, const uint8_t* d_b_keep, uint64_t n_b, uint64_t total_b, uint8_t keep_and,
+                             uint8_t keep_eq, yh_compare_cell* d_cells, uint64_t ld_cells, yh_compare_self* d_self_a,
+                             yh_compare_self* d_self_b, void* d_work, uint64_t work_bytes, void* stream, uint32_t hash_bits,
+                             yh_compare_sparse_info* d_info);
+int yh_compare_sparse_count_device(const uint64_t* d_a, const uint64_t* d_a_off, const uint8_t* d_a_keep, uint64_t n_a, uint64_t total_a,
+                                   const uint64_t* d_b, const uint64_t* d_b_off, const uint8_t* d_b_keep, uint64_t n_b, uint64_t total_b,
+                                   uint8_t keep_and, uint8_t keep_eq, void* d_work, uint64_t work_bytes, void* stream,
+                                   uint32_t hash_bits, yh_compare_sparse_info* d_info);
+int yh_compare_routed(const uint64_t* a, const uint64_t* a_off, const uint32_t* a_abund, const uint8_t* a_keep, uint64_t n_a,
+                      const uint64_t* b, const uint64_t* b_off, const uint32_t* b_abund, const uint8_t* b_keep, uint64_t n_b,
+                      uint8_t keep_and, uint8_t keep_eq, int device_id, yh_compare_cell* cells, uint64_t ld_cells,
+                      yh_compare_self* self_a, yh_compare_self* self_b, int route, yh_compare_sparse_info* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,10 @@ YH_COMPARE_TILE = 8  # samples a side of a workgroup's tile of cells (yh_compare
 YH_COMPARE_SLICE = 256  # entries of a sample staged in LDS per round
 YH_COMPARE_MAX_WINDOWS = 64  # windows a tile's walk over [0, the call's largest hash] is cut into at most
 YH_COMPARE_MAX_SAMPLES = 2048  # samples a side per call
+YH_COMPARE_RUN_SMALL = 32  # sparse route: runs of up to this many entries are flattened, longer ones get a workgroup
+YH_COMPARE_SPARSE_CHUNK = 2048  # sparse route: sorted records a workgroup of the runs kernel takes
+YH_COMPARE_SAMPLE_LOG2 = 6  # route auto groups the hashes below 2^(hash_bits - 6)
+YH_COMPARE_ROUTE_DENSE, YH_COMPARE_ROUTE_SPARSE, YH_COMPARE_ROUTE_AUTO = 0, 1, 2
 YH_LOOKUP_AUTO, YH_LOOKUP_STREAM, YH_LOOKUP_INDEXED = 0, 1, 2
 
 _ERR_NAMES = {
@@ -107,6 +111,11 @@ class CompareCell(C.Structure):
 
 class CompareSelf(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("n_kept", "sum", "sq_lo", "sq_hi")]
+
+
+class CompareSparseInfo(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_entries", "n_shared_hashes", "n_pair_updates", "longest_run", "dense_steps",
+                                          "pairs_sampled")] + [("route", C.c_uint32), ("estimated", C.c_uint32)]
 
 
 _u64p = C.POINTER(C.c_uint64)
@@ -225,6 +234,13 @@ SIGNATURES = {
                                     C.c_uint8, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _vp]),
     "yh_compare": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, C.c_uint8, C.c_uint8, C.c_int, _vp,
                              C.c_uint64, _vp, _vp]),
+    "yh_compare_sparse_work_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
+    "yh_compare_sparse_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64,
+                                           C.c_uint8, C.c_uint8, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp]),
+    "yh_compare_sparse_count_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp, C.c_uint64, C.c_uint64, C.c_uint8,
+                                                 C.c_uint8, _vp, C.c_uint64, _vp, C.c_uint32, _vp]),
+    "yh_compare_routed": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, C.c_uint8, C.c_uint8, C.c_int, _vp,
+                                    C.c_uint64, _vp, _vp, C.c_int, C.POINTER(CompareSparseInfo)]),
     "yh_hyp_test": (C.c_int, [C.c_uint64, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "yh_train_select": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.POINTER(C.c_uint64)]),
     "yh_sig_batch_read": (C.c_int, [C.POINTER(C.c_char_p), C.c_uint64, C.c_int, C.POINTER(_vp)]),

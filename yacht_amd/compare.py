@@ -10,6 +10,10 @@ A cohort that does not fit the device at once is compared in panels of consecuti
 (default 1 GiB of hashes, abundances and keep bytes, 13 bytes a hash) bounds a panel, which holds at least two samples and
 at most YH_COMPARE_MAX_SAMPLES; each panel pair p <= q is one call.  The integers of a pair do not depend on the panel it
 fell into, so neither do the files.
+
+Two routes fill the same matrix (yh_compare_routed): the dense tiles, which merge every pair in full, and the sparse route
+through the hashes that are shared.  YACHT_COMPARE_ROUTE = auto (default: chosen per call from a sample of the hash space),
+dense or sparse; the files are byte for byte the same under all three.
 """
 from __future__ import annotations
 
@@ -40,6 +44,9 @@ MATRIX_NAME = "cohort_compare_{0}.csv"
 PANEL_BYTES_ENV = "YACHT_COMPARE_PANEL_BYTES"
 PANEL_BYTES_DEFAULT = 1 << 30
 BYTES_PER_HASH = 13  # hash, abundance, keep byte
+ROUTE_ENV = "YACHT_COMPARE_ROUTE"
+ROUTES = {"dense": _lib.YH_COMPARE_ROUTE_DENSE, "sparse": _lib.YH_COMPARE_ROUTE_SPARSE, "auto": _lib.YH_COMPARE_ROUTE_AUTO}
+ROUTE_NAMES = {v: k for k, v in ROUTES.items()}
 MSG_NEEDS_TWO = "Comparing samples needs two or more --sample_file, not {0}."
 MSG_COMPARE_NEEDS_COHORT = "--compare compares the samples of a cohort with one another: it needs two or more --sample_file, not {0}."
 MSG_SCALED_DIFFER = "The samples' scale factors differ ({0} has {1}, {2} has {3}): sketches of different `scaled` are not compared."
@@ -76,10 +83,31 @@ def pack(samples: Sequence[np.ndarray], abunds=None, keeps=None):
     return values, offsets, cat_ab, cat_keep
 
 
-def compare_packed(a, b=None, keep_and: int = 0, keep_eq: int = 0, device: int = 0, ld_cells: Optional[int] = None, cells=None):
-    """yh_compare on packed sets (what pack returns); b None: the symmetric call, A against itself.  Returns (cells [n_a,
-    ld_cells] of CELL_DTYPE, self_a [n_a], self_b [n_b] of SELF_DTYPE).  cells: a buffer to write into (its columns behind
-    n_b stay as they are)."""
+def route_code(route=None) -> int:
+    """The route as yh_compare_routed takes it: "auto", "dense" or "sparse"; None reads YACHT_COMPARE_ROUTE (default auto).
+    Any other word raises ValueError."""
+    word = os.environ.get(ROUTE_ENV, "auto") if route is None else route
+    if isinstance(word, str):
+        word = word.strip().lower() or "auto"
+    if word not in ROUTES:
+        raise ValueError(f"{ROUTE_ENV if route is None else 'route'} must be one of auto, dense, sparse, not {word!r}")
+    return ROUTES[word]
+
+
+class Result(tuple):
+    """What compare_packed / compare / compare_cohort return: the tuple their callers unpack, with the routes' figures on
+    the side.  compare_packed: .info, the fields of yh_compare_sparse_info as a dict (route as its name).  compare_cohort:
+    .routes, one (p, q, route name, n_pair_updates) per panel pair."""
+    info: Optional[dict] = None
+    routes: Optional[list] = None
+
+
+def compare_packed(a, b=None, keep_and: int = 0, keep_eq: int = 0, device: int = 0, ld_cells: Optional[int] = None, cells=None,
+                   route=None):
+    """yh_compare_routed on packed sets (what pack returns); b None: the symmetric call, A against itself.  Returns (cells
+    [n_a, ld_cells] of CELL_DTYPE, self_a [n_a], self_b [n_b] of SELF_DTYPE), a Result whose .info holds the route taken and
+    its figures.  cells: a buffer to write into (its columns behind n_b stay as they are).  route: see route_code."""
+    code = route_code(route)
     lib = _lib.load()
     sym = b is None
     if sym:
@@ -90,18 +118,24 @@ def compare_packed(a, b=None, keep_and: int = 0, keep_eq: int = 0, device: int =
         cells = np.zeros((n_a, ld), dtype=CELL_DTYPE)
     self_a = np.zeros(n_a, dtype=SELF_DTYPE)
     self_b = self_a if sym else np.zeros(n_b, dtype=SELF_DTYPE)
-    _lib.check(lib.yh_compare(_ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), n_a, _ptr(b[0]), _ptr(b[1]), _ptr(b[2]), _ptr(b[3]), n_b,
-                              int(keep_and), int(keep_eq), int(device), _ptr(cells), ld, _ptr(self_a), _ptr(self_b)))
-    return cells, self_a, self_b
+    info = _lib.CompareSparseInfo()
+    _lib.check(lib.yh_compare_routed(_ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), n_a, _ptr(b[0]), _ptr(b[1]), _ptr(b[2]),
+                                     _ptr(b[3]), n_b, int(keep_and), int(keep_eq), int(device), _ptr(cells), ld, _ptr(self_a),
+                                     _ptr(self_b), code, C.byref(info)))
+    out = Result((cells, self_a, self_b))
+    out.info = {f: int(getattr(info, f)) for f, _ in info._fields_}
+    out.info["route"] = ROUTE_NAMES[out.info["route"]]
+    return out
 
 
 def compare(samples_a, samples_b=None, abunds_a=None, abunds_b=None, keeps_a=None, keeps_b=None, keep_and: int = 0,
-            keep_eq: int = 0, device: int = 0):
-    """Every sample of A against every sample of B (samples_b None: of A itself, the symmetric call) in one yh_compare.
-    A hash takes part iff its side has no keep bytes or (keep & keep_and) == keep_eq.  Returns (cells, self_a, self_b)."""
+            keep_eq: int = 0, device: int = 0, route=None):
+    """Every sample of A against every sample of B (samples_b None: of A itself, the symmetric call) in one call of
+    yh_compare_routed.  A hash takes part iff its side has no keep bytes or (keep & keep_and) == keep_eq.  Returns (cells,
+    self_a, self_b) as compare_packed does."""
     a = pack(samples_a, abunds_a, keeps_a)
     b = None if samples_b is None else pack(samples_b, abunds_b, keeps_b)
-    return compare_packed(a, b, keep_and, keep_eq, device)
+    return compare_packed(a, b, keep_and, keep_eq, device, route=route)
 
 
 def work_bytes(n_a: int, n_b: int, total_a: int, total_b: int) -> int:
@@ -116,6 +150,33 @@ def compare_device(d_a: int, d_a_off: int, d_a_abund: int, d_a_keep: int, n_a: i
     _lib.check(_lib.load().yh_compare_device(v(d_a), v(d_a_off), v(d_a_abund), v(d_a_keep), int(n_a), int(total_a), v(d_b), v(d_b_off),
                                              v(d_b_abund), v(d_b_keep), int(n_b), int(total_b), int(keep_and), int(keep_eq), v(d_cells),
                                              int(ld_cells), v(d_self_a), v(d_self_b), v(d_work), int(n_work_bytes), v(stream)))
+
+
+def sparse_work_bytes(n_a: int, n_b: int, total_a: int, total_b: int) -> int:
+    return int(_lib.load().yh_compare_sparse_work_bytes(int(n_a), int(n_b), int(total_a), int(total_b)))
+
+
+def compare_sparse_device(d_a: int, d_a_off: int, d_a_abund: int, d_a_keep: int, n_a: int, total_a: int, d_b: int, d_b_off: int,
+                          d_b_abund: int, d_b_keep: int, n_b: int, total_b: int, keep_and: int, keep_eq: int, d_cells: int,
+                          ld_cells: int, d_self_a: int, d_self_b: int, d_work: int, n_work_bytes: int, stream: int = 0,
+                          hash_bits: int = 64, d_info: int = 0) -> None:
+    """yh_compare_sparse_device: the sparse route on device buffers (addresses; 0 = NULL), enqueued on `stream` without a
+    host sync.  hash_bits: every hash is below 2**hash_bits.  d_info: room for one yh_compare_sparse_info, or 0."""
+    v = C.c_void_p
+    _lib.check(_lib.load().yh_compare_sparse_device(v(d_a), v(d_a_off), v(d_a_abund), v(d_a_keep), int(n_a), int(total_a), v(d_b),
+                                                    v(d_b_off), v(d_b_abund), v(d_b_keep), int(n_b), int(total_b), int(keep_and),
+                                                    int(keep_eq), v(d_cells), int(ld_cells), v(d_self_a), v(d_self_b), v(d_work),
+                                                    int(n_work_bytes), v(stream), int(hash_bits), v(d_info)))
+
+
+def sparse_count_device(d_a: int, d_a_off: int, d_a_keep: int, n_a: int, total_a: int, d_b: int, d_b_off: int, d_b_keep: int, n_b: int,
+                        total_b: int, keep_and: int, keep_eq: int, d_work: int, n_work_bytes: int, stream: int, hash_bits: int,
+                        d_info: int) -> None:
+    """yh_compare_sparse_count_device: the sparse route's grouping alone (records, sort, runs), its figures left in d_info."""
+    v = C.c_void_p
+    _lib.check(_lib.load().yh_compare_sparse_count_device(v(d_a), v(d_a_off), v(d_a_keep), int(n_a), int(total_a), v(d_b), v(d_b_off),
+                                                          v(d_b_keep), int(n_b), int(total_b), int(keep_and), int(keep_eq), v(d_work),
+                                                          int(n_work_bytes), v(stream), int(hash_bits), v(d_info)))
 
 
 # ---- metrics -------------------------------------------------------------------------------------------------------------------
@@ -229,10 +290,14 @@ def plan_panels(n_hashes: Sequence[int], budget: int) -> List[range]:
 
 
 def compare_cohort(n_hashes: Sequence[int], load: Callable[[range], Tuple[list, list, list]], keep_and: int = 0, keep_eq: int = 0,
-                   device: int = 0, budget: Optional[int] = None):
+                   device: int = 0, budget: Optional[int] = None, route=None):
     """All samples against all, in panels.  load(panel) returns the panel's (samples, abunds, keeps) for `pack`.  Each panel
-    pair p <= q is one yh_compare (p == q: the symmetric call); the block (q, p) is (p, q)'s transpose.  Returns (cells
-    [n, n], self rows [n], seconds inside the calls)."""
+    pair p <= q is one call (p == q: the symmetric call), on the route `route` names or chooses; the block (q, p) is
+    (p, q)'s transpose.  Returns (cells [n, n], self rows [n], seconds inside the calls), a Result whose .routes lists per
+    panel pair the route taken and its cell updates."""
+    code = route_code(route)
+    route = ROUTE_NAMES[code]
+    routes = []
     n = len(n_hashes)
     panels = plan_panels(n_hashes, panel_bytes() if budget is None else int(budget))
     cells = np.zeros((n, n), dtype=CELL_DTYPE)
@@ -244,14 +309,18 @@ def compare_cohort(n_hashes: Sequence[int], load: Callable[[range], Tuple[list, 
             pq = panels[q]
             b = None if q == p else pack(*load(pq))
             t0 = time.perf_counter()
-            got, s_a, s_b = compare_packed(a, b, keep_and, keep_eq, device)
+            res = compare_packed(a, b, keep_and, keep_eq, device, route=route)
             seconds += time.perf_counter() - t0
+            got, s_a, s_b = res
+            routes.append((p, q, res.info["route"], res.info["n_pair_updates"]))
             cells[pp.start:pp.stop, pq.start:pq.stop] = got
             self_rows[pp.start:pp.stop] = s_a
             if q != p:
                 cells[pq.start:pq.stop, pp.start:pp.stop] = got.T
                 self_rows[pq.start:pq.stop] = s_b
-    return cells, self_rows, seconds
+    out = Result((cells, self_rows, seconds))
+    out.routes = routes
+    return out
 
 
 # ---- `yacht compare` -----------------------------------------------------------------------------------------------------------
@@ -320,13 +389,23 @@ def run_files(paths: Sequence[str], stems: Sequence[str], meta: Sequence, ksize:
     """Compare the sample files and write cohort_compare.tsv and the matrices into results_folder; with residual_keeps
     (per sample uint8 [n_hashes], 1 = explained, or None = nothing explained) also cohort_compare_residual.tsv over the
     hashes whose byte is 0.  Returns the seconds inside the device calls."""
+    from .utils import logger
+
     n_hashes = [m[0] for m in meta]
-    cells, self_rows, seconds = compare_cohort(n_hashes, file_loader(paths, ksize, num_threads))
+    route = ROUTE_NAMES[route_code(None)]  # (a bad YACHT_COMPARE_ROUTE stops here, before any device work)
+    first = compare_cohort(n_hashes, file_loader(paths, ksize, num_threads), route=route)
+    cells, self_rows, seconds = first
+    routes = list(first.routes)
     write_outputs(results_folder, stems, cells, self_rows, ksize)
     if residual_keeps is not None:
-        r_cells, r_self, more = compare_cohort(n_hashes, file_loader(paths, ksize, num_threads, residual_keeps), keep_and=1, keep_eq=0)
+        second = compare_cohort(n_hashes, file_loader(paths, ksize, num_threads, residual_keeps), keep_and=1, keep_eq=0, route=route)
+        r_cells, r_self, more = second
+        routes += second.routes
         table_frame(stems, r_cells, r_self, ksize).to_csv(os.path.join(results_folder, RESIDUAL_TABLE_NAME), sep="\t", index=False)
         seconds += more
+    n_sparse = sum(1 for r in routes if r[2] == "sparse")
+    logger.info(f"{len(routes)} panel pairs: {n_sparse} sparse, {len(routes) - n_sparse} dense "
+                f"({sum(r[3] for r in routes)} cell updates on the sparse route; {ROUTE_ENV}={route})")
     return seconds
 
 
