@@ -304,6 +304,8 @@ int yh_run_device_join(yh_db* db);
  *   yh_lca / yh_lca_device, yh_db_set_taxonomy               | yes (no step state is read or written) | yes
  *   yh_lca_batch / yh_lca_batch_device,                      | yes (no step state is read or written) | yes
  *     yh_lca_rows_pack_device                                |                                       |
+ *   yh_matrix_cells_device, yh_matrix_prevalence_device,     | yes (no step state is read or written) | yes
+ *     yh_matrix_fill_device                                  |                                       |
  *   yh_db_set_stream                                         | yes (drains the old stream first)      | yes
  *   (*) the CURRENT context = the one named by the last yh_run_local*_device / yh_run_finish*_device call (0 at start).
  * Every query entry point first completes the pending stages of pipelined steps (yh_run_device_join) by itself.          */
@@ -1120,6 +1122,66 @@ int yh_compare_routed(const uint64_t* a, const uint64_t* a_off, const uint32_t* 
                       const uint64_t* b, const uint64_t* b_off, const uint32_t* b_abund, const uint8_t* b_keep, uint64_t n_b,
                       uint8_t keep_and, uint8_t keep_eq, int device_id, yh_compare_cell* cells, uint64_t ld_cells,
                       yh_compare_self* self_a, yh_compare_self* self_b, int route, yh_compare_sparse_info* info);
+
+/* ---- the organism x sample tables of a cohort (additive in ABI 8) -------------------------------------------------------------
+ * A block of a cohort ends with its compact rows (yh_run_batch_rows_unpack_device, in (reference, sample) order), the present
+ * bytes yh_presence_rows_device left beside them, and with abundances the median depth gathered at the rows.  These three
+ * entry points read them together: rows become CELLS that stay on the device block behind block, the cells of the whole
+ * cohort give per-coverage prevalence counts and per-sample depth sums, and one more pass stores the kept cells into the wide
+ * [organism][sample] matrices of one coverage.
+ *
+ * A cell is 24 bytes.  mask has one bit per coverage (bit c = present at coverage c of the call that made it, at most
+ * YH_MATRIX_MAX_SETS); depth2 is TWICE the median depth: med_match is x.0 or x.5 (yh_abund_device), so depth2 is an exact
+ * integer below 2^34, every sum of it is a 64-bit integer sum, and no result depends on the order of the additions.
+ *
+ * yh_matrix_cells_device handles every row k < min(*d_n_rows, cap_rows) with ref < N whose mask
+ *   OR over c < n_sets of (d_present[c * cap_rows + k] != 0) << c
+ * is non-zero, and writes one cell per such row, in row order: {row.sample + sample_base, row.ref, row.n_match, mask,
+ * (uint64_t)(2 * d_med[k])} (depth2 = 0 when d_med is NULL).  *d_n_cells (device) receives their number, at most cap_rows, so
+ * d_cells [cap_rows] always holds them.  It is a stable compaction -- the masks of every chunk of YH_MATRIX_CHUNK rows
+ * counted, the counts scanned by one workgroup, the cells written behind their chunk's first -- in which no atomic decides a
+ * position: two identical calls give identical bytes.  *d_n_rows is read on the device; there is no host sync.  Enqueued on
+ * the handle's stream behind pending stages; reads no handle state but N.  n_sets outside 1..YH_MATRIX_MAX_SETS:
+ * YH_ERR_INVALID_ARG.
+ *
+ * yh_matrix_prevalence_device clears d_prev [n_sets][N] and d_denom [n_sets][n_samples], then for every cell with sample <
+ * n_samples, ref < N and d_skip[sample] == 0 (d_skip NULL: nothing skipped) and every set bit c < n_sets:
+ *   d_prev[c * N + ref] += 1,   d_denom[c * n_samples + sample] += depth2.
+ * The cells of one reference arrive in runs: a wave adds a run's count with one atomic (a segmented reduction over equal
+ * ref); the depth sums go through a table in LDS keyed by sample and reach global memory once per workgroup and sample.
+ * Integer atomics only: bit-reproducible, whatever the order of the cells.  n_cells == 0 leaves both outputs cleared.
+ *
+ * yh_matrix_fill_device clears d_presence (uint8), d_n_match (uint32) and, unless NULL, d_rel (double), each
+ * [n_kept][n_samples], then every cell with bit `bit` set, sample < n_samples, d_skip[sample] == 0, ref < N and
+ * r = d_row_of_ref[ref] in [0, n_kept) stores
+ *   d_presence[r * n_samples + sample] = 1,  d_n_match[.] = n_match,
+ *   d_rel[.] = (double)depth2 / (double)d_denom_bit[sample], 0 where that sum is 0
+ * (d_denom_bit = row `bit` of d_denom; needed with d_rel).  The caller passes at most one cell per (sample, reference), so
+ * every cell owns its place: plain stores, no atomics.  d_row_of_ref[N] is -1 for a dropped reference.  The quotient equals
+ * depth / total of the host's relative abundance bit for bit: numerator and denominator are both the host's values times 2.
+ * n_kept == 0 or n_samples == 0 launches nothing; n_cells == 0 leaves cleared matrices.  n_kept > N or bit >=
+ * YH_MATRIX_MAX_SETS: YH_ERR_INVALID_ARG.
+ * Both are enqueued on the handle's stream, do not sync the host and read no handle state but N (interleaving table above:
+ * yes / yes).  Hash-range shards: nothing is built; the rows of a sharded batch are the global ones on every rank, so one
+ * rank's handle can make the cells.                                                                                       */
+#define YH_MATRIX_MAX_SETS 32
+#ifndef YH_MATRIX_CHUNK
+#define YH_MATRIX_CHUNK 1024 /* rows per chunk of the compaction: a multiple of 256 */
+#endif
+#ifndef YH_MATRIX_TILE
+#define YH_MATRIX_TILE 2048  /* cells a workgroup of the prevalence pass takes: a multiple of 256 */
+#endif
+typedef struct yh_matrix_cell { uint32_t sample, ref, n_match, mask; uint64_t depth2; } yh_matrix_cell; /* 24 bytes */
+int yh_matrix_cells_device(yh_db* db, const yh_batch_row* d_rows, const uint32_t* d_n_rows /* DEVICE */, uint64_t cap_rows,
+                           const uint8_t* d_present /* [n_sets][cap_rows] */, uint32_t n_sets, const double* d_med /* [cap_rows] or NULL */,
+                           uint32_t sample_base, yh_matrix_cell* d_cells /* [cap_rows] */, uint64_t* d_n_cells /* DEVICE */);
+int yh_matrix_prevalence_device(yh_db* db, const yh_matrix_cell* d_cells, uint64_t n_cells, uint32_t n_sets, uint32_t n_samples,
+                                const uint8_t* d_skip /* [n_samples] or NULL */, uint32_t* d_prev /* [n_sets][N] */,
+                                uint64_t* d_denom /* [n_sets][n_samples] */);
+int yh_matrix_fill_device(yh_db* db, const yh_matrix_cell* d_cells, uint64_t n_cells, uint32_t bit, uint32_t n_samples,
+                          const uint8_t* d_skip /* [n_samples] or NULL */, const int32_t* d_row_of_ref /* [N], -1: dropped */,
+                          uint64_t n_kept, const uint64_t* d_denom_bit /* [n_samples] or NULL */, uint8_t* d_presence,
+                          uint32_t* d_n_match, double* d_rel /* [n_kept][n_samples] each; d_rel may be NULL */);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,10 @@ the device time of the blocks' depth passes (YACHT_COHORT_ABUND=loop in the envi
 runs them with `yacht run --lineages FILE --lineages_rank RANK` over a synthetic lineage table (four consecutive organisms to
 a genus, four genera to a family, and so on up): gpu_lca is the device time of the blocks' yh_lca_batch_device and rows pack
 (YACHT_COHORT_LCA=loop in the environment: the HOST WALL time of one host-form yh_lca call per sample, not device time).
---commit is recorded."""
+--matrix [--matrix_min_samples M] runs the cohort with `yacht run --matrix`: gpu_matrix is the device time of the blocks' cell
+passes and of the prevalence and fill passes after the last block, matrix_files the host time of writing the tables
+(YACHT_COHORT_MATRIX=host in the environment: every cell and the tables made on the host, gpu_matrix 0); the single commands
+run without it.  --commit is recorded."""
 from __future__ import annotations
 
 import argparse
@@ -151,6 +154,8 @@ def main():
     ap.add_argument("--gather_top", type=int, default=None)
     ap.add_argument("--lineages", action="store_true")
     ap.add_argument("--lineages_rank", default="genus")
+    ap.add_argument("--matrix", action="store_true")
+    ap.add_argument("--matrix_min_samples", type=int, default=None)
     ap.add_argument("--commit", default="")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -167,7 +172,8 @@ def main():
                            min_coverage_list=COVS, outdir=out, residual=a.residual, residual_coverage=None,
                            abundance=a.abundance, gather=a.gather, gather_top=a.gather_top, gather_min_hits=1, gather_coverage=None,
                            lineages=make_lineages(tmp, a.n_refs) if a.lineages else None,
-                           lineages_rank=a.lineages_rank if a.lineages else None)
+                           lineages_rank=a.lineages_rank if a.lineages else None,
+                           matrix=a.matrix, matrix_coverage=None, matrix_min_samples=a.matrix_min_samples)
     t0 = time.perf_counter()
     phases = cohort.main(args, paths)
     wall = time.perf_counter() - t0
@@ -180,7 +186,7 @@ def main():
         od = os.path.join(tmp, f"single_{i}")
         os.makedirs(od)
         t0 = time.perf_counter()
-        run_YACHT.main(SimpleNamespace(**{**vars(args), "sample_file": p, "outdir": od}))
+        run_YACHT.main(SimpleNamespace(**{**vars(args), "sample_file": p, "outdir": od, "matrix": False, "matrix_min_samples": None}))
         single_s.append(time.perf_counter() - t0)
     from yacht_amd import hypothesis_recovery_src as hr
 
@@ -198,6 +204,9 @@ def main():
         "lineages": bool(a.lineages),
         "lineages_rank": a.lineages_rank if a.lineages else None,
         "cohort_lca": os.environ.get("YACHT_COHORT_LCA", ""),
+        "matrix": bool(a.matrix),
+        "matrix_min_samples": a.matrix_min_samples,
+        "cohort_matrix": os.environ.get("YACHT_COHORT_MATRIX", ""),
         "setup_s": round(setup_s, 1),
         "bottleneck": None,
         "cohort": {"samples": a.samples, "wall_s": round(wall, 2), "samples_per_s": round(a.samples / wall, 2),

@@ -47,6 +47,9 @@ YH_COMPARE_RUN_SMALL = 32  # sparse route: runs of up to this many entries are f
 YH_COMPARE_SPARSE_CHUNK = 2048  # sparse route: sorted records a workgroup of the runs kernel takes
 YH_COMPARE_SAMPLE_LOG2 = 6  # route auto groups the hashes below 2^(hash_bits - 6)
 YH_COMPARE_ROUTE_DENSE, YH_COMPARE_ROUTE_SPARSE, YH_COMPARE_ROUTE_AUTO = 0, 1, 2
+YH_MATRIX_MAX_SETS = 32  # coverages a cell's mask holds (yh_matrix_*)
+YH_MATRIX_CHUNK = 1024  # rows per chunk of yh_matrix_cells_device's compaction
+YH_MATRIX_TILE = 2048  # cells a workgroup of yh_matrix_prevalence_device takes
 YH_LOOKUP_AUTO, YH_LOOKUP_STREAM, YH_LOOKUP_INDEXED = 0, 1, 2
 
 _ERR_NAMES = {
@@ -241,6 +244,9 @@ SIGNATURES = {
                                                  C.c_uint8, _vp, C.c_uint64, _vp, C.c_uint32, _vp]),
     "yh_compare_routed": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, C.c_uint64, C.c_uint8, C.c_uint8, C.c_int, _vp,
                                     C.c_uint64, _vp, _vp, C.c_int, C.POINTER(CompareSparseInfo)]),
+    "yh_matrix_cells_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
+    "yh_matrix_prevalence_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "yh_matrix_fill_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),
     "yh_hyp_test": (C.c_int, [C.c_uint64, _vp, _vp, C.c_int, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "yh_train_select": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.POINTER(C.c_uint64)]),
     "yh_sig_batch_read": (C.c_int, [C.POINTER(C.c_char_p), C.c_uint64, C.c_int, C.POINTER(_vp)]),

@@ -14,6 +14,10 @@ yh_gather_batch_device per gather coverage): results/<stem>/gather_profile.tsv a
 With --lineages --lineages_rank RANK the tree is built and set once, and per block one yh_lca_batch_device and one
 yh_lca_rows_pack_device follow: results/<stem>/lca_summary.tsv and results/cohort_lca.tsv, cut at RANK (taxonomy.rank_rows).
 
+With --matrix the block's rows some coverage calls present become cells that stay on the device (yh_matrix_cells_device), and
+after the last block yh_matrix_prevalence_device and yh_matrix_fill_device make the organism x sample tables of
+yacht_amd/matrix.py: results/cohort_prevalence.tsv and results/cohort_matrix_*.tsv.
+
 Output: results/<stem>/ per sample with overlap (what a single-sample run of that file writes into results/),
 results/cohort_samples.tsv and results/cohort_presence.tsv.  Every input is checked before any device work; the
 per-sample intermediate files of the single path (multisearch CSV, list files) are not written.  Every sample is parsed
@@ -110,6 +114,11 @@ def check_inputs(args, files: List[str]) -> dict:
 
         lineages = taxonomy.lineages_option(args, len(files))
         lineages_rank = taxonomy.lineages_rank(args)
+    matrix_plan = None
+    if getattr(args, "matrix", False) or any(getattr(args, k, None) is not None for k in ("matrix_coverage", "matrix_min_samples")):
+        from . import matrix
+
+        matrix_plan = matrix.matrix_options(args, len(files))
     json_file_path = str(Path(args.json).absolute())
     paths = [str(Path(f).absolute()) for f in files]
     outdir = str(Path(args.outdir).absolute())
@@ -146,7 +155,7 @@ def check_inputs(args, files: List[str]) -> dict:
 
             raise ValueError(abundance.MSG_NO_ABUNDANCE.format(p))
         meta.append(m)
-    return dict(config=config, paths=paths, outdir=outdir, meta=meta, lineages=lineages, lineages_rank=lineages_rank)
+    return dict(config=config, paths=paths, outdir=outdir, meta=meta, lineages=lineages, lineages_rank=lineages_rank, matrix=matrix_plan)
 
 
 _LCA_TREE = None  # (parent, leaf, node_lineages) of --lineages in a process of the write pool: sent once, not with every sample
@@ -193,7 +202,7 @@ class _Device:
 
     def __init__(self, db, covs, ksize: int, ani_thresh: float, thr_table: np.ndarray, cap: int = 0, abund_samples: int = 0,
                  residual_sets: int = 0, gather_sets=(), gather_min_hits: int = 1, gather_top: int = 0, n_user: int = 0,
-                 max_samples: int = BLOCK, lca_nodes: int = 0, lca_cap: int = 0):
+                 max_samples: int = BLOCK, lca_nodes: int = 0, lca_cap: int = 0, matrix_sets: int = 0):
         """cap: compact rows a block may have before it takes the dense rows (0: BLOCK * N, at most 2^20; grows after a
         block that exceeded it).  abund_samples (--abundance): samples of the largest block; 0 = no abundance pass.
         residual_sets (--residual): the number of user coverages, the LAST residual_sets entries of covs, whose call sets
@@ -202,10 +211,13 @@ class _Device:
         gather_min_hits and at most gather_top rows per sample and coverage, for blocks of up to max_samples; empty = no
         ranking.  lca_nodes (--lineages): the nodes of the taxonomy set on db, for blocks of up to max_samples; 0 = no
         lineage pass.  lca_cap: rows of a block's lineage counts the row buffer starts with (0: LCA_ROWS_CAP, at most one
-        per cell; it grows after a block that exceeded it)."""
+        per cell; it grows after a block that exceeded it).  matrix_sets (--matrix): the number of user coverages, the LAST
+        matrix_sets entries of covs, whose present bytes become the masks of the block's cells (yh_matrix_cells_device); the
+        cells of every collected block stay on the device in matrix_cells; 0 = no cells."""
         import torch
 
         self.torch = torch
+        self.matrix_sets = int(matrix_sets)
         self.db = db
         self.dev = torch.device(f"cuda:{db.info()['device_id']}")
         self.covs = np.ascontiguousarray(covs, dtype=np.float64)
@@ -256,6 +268,21 @@ class _Device:
             self.l_n_host = torch.zeros(1, dtype=torch.int64).pin_memory()
             self._lca_alloc(int(lca_cap) if lca_cap > 0 else min(bmax * self.lca_nodes, LCA_ROWS_CAP))
             self.ev_lca = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        if self.matrix_sets > 0:  # per block: its cells (24 bytes each, at most one per compact row) and their count
+            if self.matrix_sets > self.covs.size:
+                raise ValueError(f"{self.matrix_sets} matrix coverages for {self.covs.size} coverages")
+            self.m_n = torch.zeros(1, dtype=torch.int64, device=self.dev)
+            self.m_n_host = torch.zeros(1, dtype=torch.int64).pin_memory()
+            self.m_base = 0
+            self.matrix_cells = []  # the collected blocks' cells, device-resident, in block order
+            self.ev_matrix = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+
+    def matrix_pass(self, rows, d_n_rows: int, cap: int, out, med, cells) -> None:
+        """The block's cells: one yh_matrix_cells_device over the rows, the user coverages' present bytes and (with
+        --abundance) the medians gathered at the rows.  No host sync: the count stays on the device."""
+        first = self.covs.size - self.matrix_sets  # (the forced 1.0 in front is no user coverage)
+        self.db.matrix_cells_device(rows.data_ptr(), d_n_rows, cap, out[1][first].data_ptr(), self.matrix_sets,
+                                    med.data_ptr() if med is not None else 0, self.m_base, cells.data_ptr(), self.m_n.data_ptr())
 
     def _lca_alloc(self, cap: int) -> None:
         self.l_cap = int(cap)
@@ -274,6 +301,8 @@ class _Device:
         self.vals = t.zeros((self.cap, 3), dtype=t.int32, device=self.dev)
         self.rows = t.zeros((self.cap, 5), dtype=t.int32, device=self.dev)
         self.out = self._out(self.cap)
+        if self.matrix_sets > 0:
+            self.m_cells = t.zeros((self.cap, 3), dtype=t.int64, device=self.dev)  # (engine.MATRIX_CELL_DTYPE: 24 bytes)
 
     def _out(self, cap: int):
         t = self.torch
@@ -359,10 +388,11 @@ class _Device:
                                      for m, a in zip(mins, explain_abunds)]).view(np.int32)
             self.d_x_abund = t.from_numpy(cat_ab).pin_memory().to(self.dev, non_blocking=True)
 
-    def launch(self, mins: List[np.ndarray], abunds=None, explain_abunds=None) -> int:
+    def launch(self, mins: List[np.ndarray], abunds=None, explain_abunds=None, sample_base=None) -> int:
         """Queue one block: upload, batch counts, compact rows, presence test, row count to the host.  No host sync.
         abunds (--abundance): every sample's abundances.  explain_abunds (the explain pass without --abundance): per sample
-        its abundances or None; a sample without counts every hash once.
+        its abundances or None; a sample without counts every hash once.  sample_base (--matrix): the cohort index of the
+        block's first sample (None: 0).
         Events on the caller's (legacy default) stream, which the handle's blocking stream orders against, split the
         block's device time into upload, counts + compact rows, and the presence kernel."""
         t = self.torch
@@ -390,6 +420,13 @@ class _Device:
             self.ev_abund[0].record()
             self.abundance_pass(offs, b)
             self.ev_abund[1].record()
+        if self.matrix_sets > 0:  # (behind the presence test and the abundance pass: their outputs are its inputs)
+            self.m_base = int(sample_base or 0)
+            self.ev_matrix[0].record()
+            self.matrix_pass(self.rows, self.n_rows[1].data_ptr(), self.cap, self.out,
+                             self.abund_rows[2] if self.abund is not None else None, self.m_cells)
+            self.ev_matrix[1].record()
+            self.m_n_host.copy_(self.m_n, non_blocking=True)
         total = int(offs[-1])
         self.x_block = (b, total)
         self.d_x_abund, self._x_abund_done = None, False
@@ -433,6 +470,9 @@ class _Device:
         k = int(self.n_rows_host[0])
         rows, out = self.rows, self.out
         abund_rows = self.abund_rows if self.abund is not None else None
+        if self.matrix_sets > 0:
+            timer["gpu_matrix"] += self.ev_matrix[0].elapsed_time(self.ev_matrix[1]) / 1e3
+            m_cells, m_n = self.m_cells, int(self.m_n_host[0])
         if k > self.cap:  # more entries than the compact buffers hold: the block's rows from its dense counts
             ev[0].record()
             ov = self.counts[0, :b]
@@ -455,9 +495,17 @@ class _Device:
                 self.ev_gather[0].record()
                 self.gather_pass(rows, d_k.data_ptr(), k, out, b, self.x_block[1])
                 self.ev_gather[1].record()
+            if self.matrix_sets > 0:  # (and the cells)
+                m_cells = t.zeros((max(k, 1), 3), dtype=t.int64, device=self.dev)
+                self.ev_matrix[0].record()
+                self.matrix_pass(rows, d_k.data_ptr(), k, out, abund_rows[2] if abund_rows is not None else None, m_cells)
+                self.ev_matrix[1].record()
             t0 = time.perf_counter()
             t.cuda.synchronize(self.dev)
             timer["device_wait"] += time.perf_counter() - t0
+            if self.matrix_sets > 0:
+                timer["gpu_matrix"] += self.ev_matrix[0].elapsed_time(self.ev_matrix[1]) / 1e3
+                m_n = int(self.m_n.item())
             timer["gpu_counts"] += ev[0].elapsed_time(ev[1]) / 1e3
             timer["gpu_presence"] += ev[1].elapsed_time(ev[2]) / 1e3
             if self.residual_sets > 0:
@@ -466,6 +514,8 @@ class _Device:
                 timer["gpu_gather"] += self.ev_gather[0].elapsed_time(self.ev_gather[1]) / 1e3
             timer["dense_fallback_blocks"] += 1
             self._alloc(int(k * 1.25) + 1)  # (the next blocks: compact rows again)
+        if self.matrix_sets > 0:  # the block's cells stay on the device: one device-to-device copy behind the earlier blocks'
+            self.matrix_cells.append(m_cells[:m_n].clone())
         t0 = time.perf_counter()
         got = (rows[:k].cpu().numpy().view(np.uint32), out[0][:, :k].cpu().numpy(), out[1][:, :k].cpu().numpy(),
                out[2][:, :k].cpu().numpy().view(np.uint32))
@@ -517,7 +567,9 @@ def main(args, files: List[str]) -> dict:
     YACHT_COHORT_GATHER=loop), gpu_lca and lca_repacked_blocks (only with --lineages: device time of the block's
     yh_lca_batch_device and rows pack -- under YACHT_COHORT_LCA=loop the HOST WALL time of every sample's host-form yh_lca call,
     not device time -- and the blocks whose rows were packed a second time into a larger buffer), gpu_compare (only with
-    --compare: the HOST WALL time of the host-form yh_compare calls after the blocks, uploads and downloads included), d2h, assemble, writes (what the write pool had left after the last block), cohort_files (the two
+    --compare: the HOST WALL time of the host-form yh_compare calls after the blocks, uploads and downloads included), gpu_matrix and matrix_files (only with --matrix: device time of the blocks' cell passes and of
+    the prevalence and fill passes after the last block -- 0 under YACHT_COHORT_MATRIX=host -- and the host time of writing the
+    tables), d2h, assemble, writes (what the write pool had left after the last block), cohort_files (the two
     cohort tables), total."""
     timer = {k: 0.0 for k in ("check", "db", "table", "device_setup", "parse_wait", "device_wait", "gpu_h2d", "gpu_counts",
                               "gpu_presence", "gpu_abund", "gpu_explain", "gpu_gather", "d2h", "assemble", "writes", "cohort_files", "dense_fallback_blocks", "total")}
@@ -586,11 +638,20 @@ def main(args, files: List[str]) -> dict:
         timer["gpu_lca"] = timer["lca_repacked_blocks"] = 0.0
     # YACHT_COHORT_LCA=loop: every sample's lineage counts by its own host-form yh_lca call (A/B checks; the same files)
     device_lca = tree is not None and os.environ.get("YACHT_COHORT_LCA") != "loop"
+    matrix_plan = plan["matrix"]  # (--matrix_coverage, --matrix_min_samples, YACHT_COHORT_MATRIX=host) or None
+    mcol = None
+    if matrix_plan is not None:  # the organism x sample tables: the blocks' cells stay on the device (matrix.Collector)
+        from . import matrix
+
+        timer["gpu_matrix"] = timer["matrix_files"] = 0.0
+        mcol = matrix.Collector(db.n_refs, len(paths), len(user_covs), want_abundance, matrix_plan[2])
+    device_matrix = mcol is not None and not matrix_plan[2]
     dev = _Device(db, covs, ksize, ani_thresh, t_thr, abund_samples=min(BLOCK, len(paths)) if want_abundance else 0,
                   residual_sets=len(user_covs) if device_explain else 0,
                   **{**(dict(gather_sets=gather_idx, gather_min_hits=gather_plan[1], gather_top=gather_top, n_user=len(user_covs),
                              max_samples=len(paths)) if device_gather else {}),
-                     **(dict(lca_nodes=len(tree[0]), max_samples=len(paths)) if device_lca else {})})
+                     **(dict(lca_nodes=len(tree[0]), max_samples=len(paths)) if device_lca else {}),
+                     **(dict(matrix_sets=len(user_covs)) if device_matrix else {})})
     timer["device_setup"] = time.perf_counter() - t0
 
     blocks = [list(range(i, min(i + BLOCK, len(paths)))) for i in range(0, len(paths), BLOCK)]
@@ -669,6 +730,8 @@ def main(args, files: List[str]) -> dict:
                 total = int(abunds[s].sum(dtype=np.uint64))
                 frames = [abundance.append_columns(f, *depth, total) for f in frames]
             frames = ry.trim_results(frames)
+            if mcol is not None and (recomputed or not device_matrix):  # (the device's cells of a recomputed sample are skipped)
+                mcol.add_host(i, refs, frames if has_raw else frames[1:])
             explained = ranked = lineage = None
             if want_sigs:
                 call_sets = [refs[df["in_sample_est"].to_numpy().astype(bool)] for df in (frames if has_raw else frames[1:])]
@@ -740,7 +803,8 @@ def main(args, files: List[str]) -> dict:
                 mins, abunds = [x[0] for x in mins], [x[1] for x in mins]
             timer["parse_wait"] += time.perf_counter() - t0
             parsing = parse(blocks[j + 1]) if j + 1 < len(blocks) else []
-            b = dev.launch(mins, abunds if want_abundance else None, abunds if (device_explain or device_gather or device_lca) and not want_abundance else None)
+            b = dev.launch(mins, abunds if want_abundance else None, abunds if (device_explain or device_gather or device_lca) and not want_abundance else None,
+                           **(dict(sample_base=block[0]) if device_matrix else {}))
             if pending is not None:
                 assemble(*pending)  # (block j - 1 on the host while block j is on the device and block j + 1 is parsed)
             pending = (block, mins, dev.collect(b, timer), abunds, sigs)
@@ -750,6 +814,11 @@ def main(args, files: List[str]) -> dict:
         for f in futures:
             f.result()
         timer["writes"] = time.perf_counter() - t0  # (the part of the writes not hidden behind the device and the assembly)
+        if mcol is not None:  # (while the database is resident: the passes are enqueued on its handle)
+            for cells in dev.matrix_cells if device_matrix else ():
+                mcol.add_device(cells)
+            mcol.finish(results_folder, names, [sample_stem(p) for p in paths], user_covs, matrix_plan[0], matrix_plan[1],
+                        db, dev.torch, dev.dev, timer)
     finally:
         parse_pool.shutdown(wait=True)
         pool.shutdown(wait=True)

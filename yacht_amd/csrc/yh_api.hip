@@ -5,6 +5,7 @@
 #include "yh_explain.h"
 #include "yh_gather.h"
 #include "yh_lca.h"
+#include "yh_matrix.h"
 #include "yh_sort.h"
 #include "yh_pack.h"
 
@@ -1506,6 +1507,52 @@ int yh_lca_rows_pack_device(yh_db* db, const uint64_t* d_counts, uint32_t n_samp
     YH_TRY(pipe_join(db));
     fin_join(db);
     return yh_q_lca_rows_pack(db, yh_lca_taxonomy(db), (const u64*)d_counts, n_samples, d_rows, cap_rows, (u64*)d_n_rows);
+}
+
+// ---- the organism x sample tables of a cohort (yh_matrix.hip) ------------------------------------------------------------
+static bool matrix_sets_ok(uint32_t n_sets) {
+    if (n_sets >= 1 && n_sets <= YH_MATRIX_MAX_SETS) return true;
+    yh_set_error("n_sets must be 1..%d: a cell's mask has one bit per coverage", YH_MATRIX_MAX_SETS);
+    return false;
+}
+
+int yh_matrix_cells_device(yh_db* db, const yh_batch_row* d_rows, const uint32_t* d_n_rows, uint64_t cap_rows, const uint8_t* d_present,
+                           uint32_t n_sets, const double* d_med, uint32_t sample_base, yh_matrix_cell* d_cells, uint64_t* d_n_cells) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (!matrix_sets_ok(n_sets)) return YH_ERR_INVALID_ARG;
+    if (!d_n_rows || !d_n_cells || (cap_rows && (!d_rows || !d_present || !d_cells))) { yh_set_error("null device pointer"); return YH_ERR_INVALID_ARG; }
+    if (cap_rows > (1ull << 40)) { yh_set_error("cap_rows out of range"); return YH_ERR_INVALID_ARG; }
+    YH_TRY(db_select(db));
+    YH_TRY(pipe_join(db));
+    fin_join(db);  // (rows the rows pack / unpack wrote on the finish stream)
+    return yh_q_matrix_cells(db, d_rows, d_n_rows, cap_rows, d_present, n_sets, d_med, sample_base, d_cells, (u64*)d_n_cells);
+}
+
+int yh_matrix_prevalence_device(yh_db* db, const yh_matrix_cell* d_cells, uint64_t n_cells, uint32_t n_sets, uint32_t n_samples,
+                                const uint8_t* d_skip, uint32_t* d_prev, uint64_t* d_denom) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (!matrix_sets_ok(n_sets)) return YH_ERR_INVALID_ARG;
+    if ((n_cells && !d_cells) || (db->n_refs && !d_prev) || (n_samples && !d_denom)) { yh_set_error("null device pointer"); return YH_ERR_INVALID_ARG; }
+    YH_TRY(db_select(db));
+    YH_TRY(pipe_join(db));
+    return yh_q_matrix_prevalence(db, d_cells, n_cells, n_sets, n_samples, d_skip, d_prev, (u64*)d_denom);
+}
+
+int yh_matrix_fill_device(yh_db* db, const yh_matrix_cell* d_cells, uint64_t n_cells, uint32_t bit, uint32_t n_samples,
+                          const uint8_t* d_skip, const int32_t* d_row_of_ref, uint64_t n_kept, const uint64_t* d_denom_bit,
+                          uint8_t* d_presence, uint32_t* d_n_match, double* d_rel) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (bit >= YH_MATRIX_MAX_SETS) { yh_set_error("bit must be below %d", YH_MATRIX_MAX_SETS); return YH_ERR_INVALID_ARG; }
+    if (n_kept > db->n_refs) { yh_set_error("n_kept exceeds the number of references"); return YH_ERR_INVALID_ARG; }
+    const bool any = n_kept != 0 && n_samples != 0;
+    if ((any && (!d_presence || !d_n_match)) || (any && n_cells && (!d_cells || !d_row_of_ref)) || (any && d_rel && !d_denom_bit)) {
+        yh_set_error("null device pointer");
+        return YH_ERR_INVALID_ARG;
+    }
+    YH_TRY(db_select(db));
+    YH_TRY(pipe_join(db));
+    return yh_q_matrix_fill(db, d_cells, n_cells, bit, n_samples, d_skip, d_row_of_ref, n_kept, (const u64*)d_denom_bit, d_presence,
+                            d_n_match, d_rel);
 }
 
 int yh_lca_batch(yh_db* db, const uint64_t* samples, const uint64_t* sample_offsets, const uint32_t* abund, uint32_t n_samples,

@@ -109,6 +109,8 @@ GATHER_ROW_DTYPE = np.dtype([("ref", np.uint32), ("n_overlap", np.uint32), ("n_u
                              ("w_unique", np.uint64)])
 # one row of RefDB.lca_rows_pack_device (include/yacht_hip.h: yh_lca_row)
 LCA_ROW_DTYPE = np.dtype([("sample", np.uint32), ("node", np.uint32), ("n_hashes", np.uint64), ("w_hashes", np.uint64)])
+# yh_matrix_cell: one (sample, reference) some coverage calls present; mask = one bit per coverage, depth2 = twice the median depth
+MATRIX_CELL_DTYPE = np.dtype([("sample", np.uint32), ("ref", np.uint32), ("n_match", np.uint32), ("mask", np.uint32), ("depth2", np.uint64)])
 
 
 def check_candidates(cand, n_refs: int) -> np.ndarray:
@@ -464,6 +466,32 @@ class RefDB:
             raise ValueError(f"cap_rows must be >= 0, not {cap_rows}")
         _lib.check(self._lib.yh_lca_rows_pack_device(self._h, C.c_void_p(d_counts), n_samples, C.c_void_p(d_rows), int(cap_rows),
                                                      C.c_void_p(d_n_rows)))
+
+    # ---- the organism x sample tables of a cohort (yh_matrix.hip; yacht_amd.matrix drives them) ----------------------------
+    def matrix_cells_device(self, d_rows: int, d_n_rows: int, cap_rows: int, d_present: int, n_sets: int, d_med: int, sample_base: int,
+                            d_cells: int, d_n_cells: int) -> None:
+        """yh_matrix_cells_device: the block's compact rows, their count (device), uint8 [n_sets][cap_rows] present bytes and
+        float64 [cap_rows] medians (0: none) in; the rows some coverage calls present as cells of MATRIX_CELL_DTYPE in row
+        order and their number as one uint64 at d_n_cells (device) out.  Does not synchronize the host."""
+        _lib.check(self._lib.yh_matrix_cells_device(self._h, C.c_void_p(d_rows), C.c_void_p(d_n_rows), int(cap_rows), C.c_void_p(d_present),
+                                                    int(n_sets), C.c_void_p(d_med), int(sample_base), C.c_void_p(d_cells),
+                                                    C.c_void_p(d_n_cells)))
+
+    def matrix_prevalence_device(self, d_cells: int, n_cells: int, n_sets: int, n_samples: int, d_skip: int, d_prev: int,
+                                 d_denom: int) -> None:
+        """yh_matrix_prevalence_device: uint32 [n_sets][N] samples-present counts and uint64 [n_sets][n_samples] sums of depth2
+        of the cells (cleared first); d_skip: uint8 [n_samples] or 0.  Does not synchronize the host."""
+        _lib.check(self._lib.yh_matrix_prevalence_device(self._h, C.c_void_p(d_cells), int(n_cells), int(n_sets), int(n_samples),
+                                                         C.c_void_p(d_skip), C.c_void_p(d_prev), C.c_void_p(d_denom)))
+
+    def matrix_fill_device(self, d_cells: int, n_cells: int, bit: int, n_samples: int, d_skip: int, d_row_of_ref: int, n_kept: int,
+                           d_denom_bit: int, d_presence: int, d_n_match: int, d_rel: int) -> None:
+        """yh_matrix_fill_device: the [n_kept][n_samples] matrices of coverage `bit` (uint8 presence, uint32 n_match, float64
+        relative abundance or 0 for none), cleared first; d_row_of_ref: int32 [N], -1 for a dropped reference.  Does not
+        synchronize the host."""
+        _lib.check(self._lib.yh_matrix_fill_device(self._h, C.c_void_p(d_cells), int(n_cells), int(bit), int(n_samples), C.c_void_p(d_skip),
+                                                   C.c_void_p(d_row_of_ref), int(n_kept), C.c_void_p(d_denom_bit), C.c_void_p(d_presence),
+                                                   C.c_void_p(d_n_match), C.c_void_p(d_rel)))
 
     def gather(self, sample, cand, abund=None, min_hits: int = 1, cap_rows: Optional[int] = None, want_owner: bool = False):
         """The candidates ranked by the sample hashes each adds (yh_gather): round after round the candidate holding the

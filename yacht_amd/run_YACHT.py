@@ -91,6 +91,18 @@ ARGUMENTS = (
                             "Bray-Curtis and cosine, and results/cohort_compare_<metric>.csv matrices as `sourmash compare --csv` "
                             "writes them; with --residual also results/cohort_compare_residual.tsv, the same table over the hashes "
                             "the call set of --residual_coverage does not explain.  `yacht compare` does the same without a database.")),
+    ("--matrix", dict(action="store_true",
+                      help="Also write the cohort's organism x sample tables (two or more sample files): "
+                           "results/cohort_prevalence.tsv, per min_coverage and organism the samples it is present in, and "
+                           "results/cohort_matrix_presence.tsv and results/cohort_matrix_num_matches.tsv, one row per organism "
+                           "and one column per sample at --matrix_coverage; with --abundance also "
+                           "results/cohort_matrix_relative_abundance.tsv.")),
+    ("--matrix_coverage", dict(type=float, default=None,
+                               help="The --min_coverage_list value whose wide tables are written (with --matrix; default: the "
+                                    "smallest value of the list).")),
+    ("--matrix_min_samples", dict(type=int, default=None,
+                                  help="Keep an organism in the wide tables only if it is present in at least this many samples "
+                                       "at --matrix_coverage (with --matrix; default: 1).")),
 )
 
 # messages the reference raises with (callers and its tests match on them)
@@ -179,6 +191,10 @@ def main(args) -> None:
         from . import compare
 
         raise ValueError(compare.MSG_COMPARE_NEEDS_COHORT.format(len(files)))
+    if getattr(args, "matrix", False) or any(getattr(args, k, None) is not None for k in ("matrix_coverage", "matrix_min_samples")):
+        from . import matrix
+
+        matrix.matrix_options(args, len(files))  # (ValueError before anything is written or any device work)
     if want_residual or getattr(args, "residual_coverage", None) is not None:
         from . import residual
 
