@@ -304,6 +304,8 @@ int yh_run_device_join(yh_db* db);
  *   yh_lca / yh_lca_device, yh_db_set_taxonomy               | yes (no step state is read or written) | yes
  *   yh_lca_batch / yh_lca_batch_device,                      | yes (no step state is read or written) | yes
  *     yh_lca_rows_pack_device                                |                                       |
+ *   yh_classify_sets / yh_classify_sets_device,              | yes (no step state is read or written) | yes
+ *     yh_classify_segments                                   |                                       |
  *   yh_matrix_cells_device, yh_matrix_prevalence_device,     | yes (no step state is read or written) | yes
  *     yh_matrix_fill_device                                  |                                       |
  *   yh_db_set_stream                                         | yes (drains the old stream first)      | yes
@@ -714,6 +716,72 @@ int yh_lca_batch(yh_db* db, const uint64_t* samples, const uint64_t* sample_offs
                  uint32_t* node, uint64_t* counts);
 int yh_lca_rows_pack_device(yh_db* db, const uint64_t* d_counts /* [n_samples][n_nodes][2] */, uint32_t n_samples,
                             yh_lca_row* d_rows, uint64_t cap_rows, uint64_t* d_n_rows /* DEVICE */);
+
+/* ---- a taxon for every RECORD: many sets looked up at once, the LCA folded per set (additive to ABI 8) -----------------------
+ * yh_lca* answer for a whole sample; an assembly or a long-read run asks the same question per contig, bin or read -- 10^5 to
+ * 10^7 records, where the batched pass takes 256 samples and 16 bytes per (sample, node) cell.  This pass takes the sketches of
+ * many records as ONE CSR, as yh_sketch_segments_device leaves it in HBM, and writes one row of 16 bytes per record, whatever
+ * the number of nodes.
+ * yh_classify_sets_device runs under the taxonomy currently set.  node(h) is exactly what yh_lca_device defines: YH_LCA_NONE when
+ * no reference holds h (which includes h above the database's largest hash), leaf[j] when reference j is the single holder,
+ * lca_shared[gi] when the hash is shared.  Set s owns d_mins[off[s] .. off[s + 1]), strictly ascending INSIDE the set; there is
+ * no order across sets and the same hash may sit in many sets; equal neighbouring offsets are an empty set.  Every set s gets
+ * d_rows[s]:
+ *   n_kept = off[s + 1] - off[s]
+ *   n_hit  = entries with node(h) != YH_LCA_NONE
+ *   n_root = entries with node(h) == 0
+ *   node   = the LCA over the nodes of the INFORMATIVE hits, those with node(h) neither YH_LCA_NONE nor 0; 0 when there are hits
+ *            but none is informative; YH_LCA_NONE when n_hit == 0 (an empty set: {YH_LCA_NONE, 0, 0, 0})
+ * A root hit carries no information -- a k-mer two superkingdoms share, or an organism without a lineage -- so it is counted and
+ * kept out of the fold: one such k-mer does not send a 50 kb contig to the root.  node == 0 with informative hits present means
+ * that those hits disagree at the top.  With d_node given, d_node[e] = node(d_mins[e]) for every entry e < total.
+ * LCA is associative, commutative and idempotent on a validated tree and the counts are integer sums: a row depends neither on
+ * arrival order nor on the tiling, and two runs give the same bytes.  The rows are dense, one per set at its own index: no
+ * atomic or scan decides a position, there is no capacity, and EVERY row is written by the call -- nothing of an earlier call
+ * survives inside [0, n_sets).
+ * `total` is the caller's copy of off[n_sets]; it sizes the launches.  The offsets are TRUSTED, as in yh_sketch_segments_device:
+ * they must ascend from 0 to total and stay inside d_mins and d_node.  The search for an entry's set is clamped to the table, so
+ * a bad table gives wrong rows and never an access outside d_off[0 .. n_sets], d_rows[0 .. n_sets) or the first `total` entries
+ * of d_mins and d_node.
+ * How it runs: a workgroup takes a tile of YH_CLASSIFY_TILE consecutive entries and ignores set borders for the probe (the
+ * directory probe and the one dependent 4-byte read of yh_lca_device); every entry finds its set between those of the tile's
+ * first and last entry; a segmented reduction -- shuffles inside a 64-entry row, one wave over the rows' partials -- folds
+ * every run, a set that lies inside the tile writes its row, and the tile's first and last partial go to a carry record; a
+ * second small launch joins the carries (a set that spans m tiles is a chain of m joins) and writes the rows of empty sets.  No
+ * atomics.  32 bytes per tile come from the handle's buffer cache.  The join is ONE lane per set that crosses a tile border: a
+ * set of m tiles is 2 m dependent reads in that lane -- nothing for contigs, bins or reads (a bin of 5 000 hashes is five
+ * tiles), but a single set of 10^8 entries would be a walk of 2 x 10^5 records by one lane: correct, and slow.  Such a set is
+ * a sample, not a record: yh_lca_device is the call for it.
+ * Like yh_lca_device it reads no step context, batch slot or work list (interleaving table above: yes / yes), completes pending
+ * pipelined stages first, is enqueued on the handle's stream and does not sync the host.  n_sets == 0 (n_seg == 0 for
+ * yh_classify_segments) is YH_OK and does nothing, whatever the handle supports: it is looked at before the taxonomy is.  An empty database or total == 0: every row {YH_LCA_NONE, n_kept, 0, 0} (and every d_node entry YH_LCA_NONE).
+ * YH_ERR_INVALID_ARG: n_sets >= 2^32 or total >= 2^32.  YH_ERR_UNSUPPORTED exactly where yh_lca_device returns it: no taxonomy, a
+ * handle without directory or index, ghosts registered.
+ * yh_classify_sets is the synchronous host form (total = off[n_sets]): it validates the offsets (ascending from 0:
+ * YH_ERR_INVALID_ARG) and every set's ordering (YH_ERR_UNSORTED), then uploads, runs and downloads.
+ * yh_classify_segments is the path from sequence to rows: seq holds n_seg records cut by seg_off[n_seg + 1] (validated as by
+ * yh_sketch_segments: from 0 to n_bytes, not descending; n_bytes < 2^32, n_seg < 2^32, ksize 1..255).  The sequence goes up in
+ * pieces under the hashing, yh_sketch_segments' kernels leave one sketch per record in working memory from the handle's buffer
+ * cache, yh_classify_sets_device runs on that CSR, and only the n_seg rows and *n_kept_total (the entries of all sketches) come
+ * back: the sketches never cross the bus.  Sizing and the retry for a sequence that keeps more hashes than the first capacity
+ * holds are yh_sketch_segments'.  max_hash is that of the sketches the database was built from: the handle keeps only its
+ * largest hash, so a max_hash BELOW that is refused (YH_ERR_INVALID_ARG) and the caller answers for the rest (yacht_amd checks
+ * `scaled` against the training config).  Synchronous; uses the handle's stream and device.
+ * Hash-range shards: nothing is built.
+ * (No reference counterpart; nearest elsewhere: `sourmash lca classify`.)                                                      */
+#ifndef YH_CLASSIFY_TILE
+#define YH_CLASSIFY_TILE 1024 /* consecutive ENTRIES of mins a lookup workgroup takes */
+#endif
+typedef struct yh_classify_row {
+    uint32_t node, n_kept, n_hit, n_root;
+} yh_classify_row; /* 16 bytes */
+int yh_classify_sets_device(yh_db* db, const uint64_t* d_mins, const uint64_t* d_off /* [n_sets + 1] */, uint64_t n_sets,
+                            uint64_t total /* caller's copy of off[n_sets]; sizes launches */,
+                            yh_classify_row* d_rows /* [n_sets] */, uint32_t* d_node /* [total] or NULL */);
+int yh_classify_sets(yh_db* db, const uint64_t* mins, const uint64_t* off, uint64_t n_sets, yh_classify_row* rows,
+                     uint32_t* node /* or NULL */);
+int yh_classify_segments(yh_db* db, const uint8_t* seq, uint64_t n_bytes, const uint64_t* seg_off, uint64_t n_seg, int ksize,
+                         uint64_t seed, uint64_t max_hash, yh_classify_row* rows /* [n_seg] */, uint64_t* n_kept_total);
 
 /* ---- the subset words of a block in compact form (ABI 5) ----------------------------------------------------------------
  * Between the two halves of a batched hash-range run every rank needs the OR of all ranks' subset words.  The dense row

@@ -39,6 +39,7 @@ YH_GATHER_NOBODY = 0xFFFFFFFF  # an owner entry: no reference took the hash
 YH_LCA_MAX_DEPTH = 16  # deepest node of a taxonomy (yh_db_set_taxonomy)
 YH_LCA_NONE = 0xFFFFFFFF  # a node entry: no reference holds the hash
 YH_LCA_BATCH_TILE = 1024
+YH_CLASSIFY_TILE = 1024  # consecutive entries of the sets a lookup workgroup of yh_classify_sets_device takes
 YH_COMPARE_TILE = 8  # samples a side of a workgroup's tile of cells (yh_compare*)
 YH_COMPARE_SLICE = 256  # entries of a sample staged in LDS per round
 YH_COMPARE_MAX_WINDOWS = 64  # windows a tile's walk over [0, the call's largest hash] is cut into at most
@@ -209,6 +210,9 @@ SIGNATURES = {
     "yh_lca_batch_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp]),
     "yh_lca_batch": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp]),
     "yh_lca_rows_pack_device": (C.c_int, [_vp, _vp, C.c_uint32, _vp, C.c_uint64, _vp]),
+    "yh_classify_sets_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp]),
+    "yh_classify_sets": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp]),
+    "yh_classify_segments": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, _vp, C.POINTER(C.c_uint64)]),
     "yh_host_alloc": (C.c_int, [C.POINTER(_vp), C.c_uint64]),
     "yh_host_free": (C.c_int, [_vp]),
     "yh_db_nshared_device": (C.c_int, [_vp, _vp]),

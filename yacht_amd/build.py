@@ -17,9 +17,9 @@ LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libyacht_hip.so")
 EXE_PATH = os.path.join(LIB_DIR, "run_yacht_train_core")
 
-LIB_SOURCES = ["yh_api.hip", "yh_build.hip", "yh_sort.hip", "yh_query.hip", "yh_batch.hip", "yh_pairwise.hip", "yh_sketch.hip", "yh_sigread.hip", "yh_pack.hip", "yh_presence.hip", "yh_abund.hip", "yh_explain.hip", "yh_gather.hip", "yh_lca.hip", "yh_compare.hip", "yh_compare_sparse.hip", "yh_matrix.hip", "yh_hyp.cpp"]
+LIB_SOURCES = ["yh_api.hip", "yh_build.hip", "yh_sort.hip", "yh_query.hip", "yh_batch.hip", "yh_pairwise.hip", "yh_sketch.hip", "yh_sigread.hip", "yh_pack.hip", "yh_presence.hip", "yh_abund.hip", "yh_explain.hip", "yh_gather.hip", "yh_lca.hip", "yh_classify.hip", "yh_compare.hip", "yh_compare_sparse.hip", "yh_matrix.hip", "yh_hyp.cpp"]
 EXE_SOURCES = ["train_core_main.cpp"]
-HEADERS = ["yh_common.h", "yh_lookup.h", "yh_abund.h", "yh_explain.h", "yh_gather.h", "yh_lca.h", "yh_sigread.h", "yh_sort.h", "yh_binom.h", "yh_compare.h", "yh_matrix.h", os.path.join(REPO_DIR, "include", "yacht_hip.h")]
+HEADERS = ["yh_common.h", "yh_lookup.h", "yh_abund.h", "yh_explain.h", "yh_gather.h", "yh_lca.h", "yh_sketch.h", "yh_sigread.h", "yh_sort.h", "yh_binom.h", "yh_compare.h", "yh_matrix.h", os.path.join(REPO_DIR, "include", "yacht_hip.h")]
 ARCH = "gfx950"
 
 

@@ -1,7 +1,7 @@
 """`yacht` command line for the hot-path commands: `yacht train` and `yacht run`
 (reference src/yacht/__init__.py:54-136 dispatches the same sub-commands to the same
-add_arguments/main pairs), plus `yacht sketch ref|sample` on the HIP sketcher and `yacht compare`
-(sample against sample, no database).  The reference's
+add_arguments/main pairs), plus `yacht sketch ref|sample` on the HIP sketcher, `yacht compare`
+(sample against sample, no database) and `yacht classify` (a taxon per contig or read).  The reference's
 other sub-commands (download, convert) need the network / NCBI taxonomy tools and are out of this
 repository's scope.
 
@@ -13,7 +13,7 @@ from __future__ import annotations
 import argparse
 import sys
 
-from . import compare, make_training_data_from_sketches, run_YACHT, sketch
+from . import classify, compare, make_training_data_from_sketches, run_YACHT, sketch
 from .utils import __version__
 
 OUT_OF_SCOPE = ("download", "convert")
@@ -43,6 +43,10 @@ def build_parser() -> argparse.ArgumentParser:
                           formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     compare.add_arguments(cmp_)
     cmp_.set_defaults(func=compare.main)
+    cls = sub.add_parser("classify", description="Classify every record of FASTA / FASTQ files: the lowest common ancestor of its k-mers' holders",
+                         formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    classify.add_arguments(cls)
+    cls.set_defaults(func=classify.main)
     for name in OUT_OF_SCOPE:
         sub.add_parser(name, add_help=False)
     return parser

@@ -5,6 +5,7 @@
 #include "yh_explain.h"
 #include "yh_gather.h"
 #include "yh_lca.h"
+#include "yh_sketch.h"
 #include "yh_matrix.h"
 #include "yh_sort.h"
 #include "yh_pack.h"
@@ -1507,6 +1508,159 @@ int yh_lca_rows_pack_device(yh_db* db, const uint64_t* d_counts, uint32_t n_samp
     YH_TRY(pipe_join(db));
     fin_join(db);
     return yh_q_lca_rows_pack(db, yh_lca_taxonomy(db), (const u64*)d_counts, n_samples, d_rows, cap_rows, (u64*)d_n_rows);
+}
+
+// ---- a taxon for every record: many sets looked up at once, the LCA folded per set (yh_classify.hip) ------------------------
+int yh_classify_sets_device(yh_db* db, const uint64_t* d_mins, const uint64_t* d_off, uint64_t n_sets, uint64_t total,
+                            yh_classify_row* d_rows, uint32_t* d_node) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if ((n_sets >> 32) || (total >> 32)) { yh_set_error("yh_classify_sets takes fewer than 2^32 sets and 2^32 entries"); return YH_ERR_INVALID_ARG; }
+    if (n_sets == 0) return YH_OK;  // (nothing to do: before the handle is asked what it supports)
+    YH_TRY(lca_supported(db));
+    if (!d_off || !d_rows || (total && !d_mins)) { yh_set_error("null device pointer"); return YH_ERR_INVALID_ARG; }
+    YH_TRY(db_select(db));
+    YH_TRY(pipe_join(db));  // (no step context, batch slot or work list is read or written: nothing else to note)
+    return yh_q_classify_sets(db, yh_lca_taxonomy(db), (const u64*)d_mins, (const u64*)d_off, n_sets, total, d_rows, d_node);
+}
+
+int yh_classify_sets(yh_db* db, const uint64_t* mins, const uint64_t* off, uint64_t n_sets, yh_classify_row* rows, uint32_t* node) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (n_sets >> 32) { yh_set_error("yh_classify_sets takes fewer than 2^32 sets and 2^32 entries"); return YH_ERR_INVALID_ARG; }
+    if (!off || (n_sets && !rows)) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+    if (off[0] != 0) { yh_set_error("set offsets start at 0"); return YH_ERR_INVALID_ARG; }
+    for (u64 s = 0; s < n_sets; ++s)
+        if (off[s + 1] < off[s]) { yh_set_error("set offsets must not descend (set %llu)", s); return YH_ERR_INVALID_ARG; }
+    const u64 total = off[n_sets];
+    if (total >> 32) { yh_set_error("yh_classify_sets takes fewer than 2^32 sets and 2^32 entries"); return YH_ERR_INVALID_ARG; }
+    if (total && !mins) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+    for (u64 s = 0; s < n_sets; ++s)
+        if (yh_q_check_sorted_host((const u64*)mins + off[s], off[s + 1] - off[s]) != YH_OK) {
+            yh_set_error("set %llu is not strictly ascending", s);
+            return YH_ERR_UNSORTED;
+        }
+    if (n_sets == 0) return YH_OK;
+    YH_TRY(lca_supported(db));
+    YH_TRY(db_select(db));
+    u64 *d_s = nullptr, *d_o = nullptr;
+    u8* d_out = nullptr;  // the rows, then the nodes
+    int rc = YH_OK;
+    do {
+        if (yh_tmalloc(db, (void**)&d_s, std::max<u64>(total, 2) * sizeof(u64)) != hipSuccess ||
+            yh_tmalloc(db, (void**)&d_o, (n_sets + 1) * sizeof(u64)) != hipSuccess ||
+            yh_tmalloc(db, (void**)&d_out, n_sets * sizeof(yh_classify_row) + std::max<u64>(total, 4) * sizeof(u32)) != hipSuccess) {
+            yh_set_error("device allocation failed"); rc = YH_ERR_OOM; break;
+        }
+        if ((total && hipMemcpyAsync(d_s, mins, total * sizeof(u64), hipMemcpyHostToDevice, db->stream) != hipSuccess) ||
+            hipMemcpyAsync(d_o, off, (n_sets + 1) * sizeof(u64), hipMemcpyHostToDevice, db->stream) != hipSuccess) {
+            yh_set_error("classify upload failed"); rc = YH_ERR_HIP; break;
+        }
+        yh_classify_row* const d_rows = (yh_classify_row*)d_out;
+        u32* const d_node = node ? (u32*)(d_out + n_sets * sizeof(yh_classify_row)) : nullptr;
+        if ((rc = yh_classify_sets_device(db, (const uint64_t*)d_s, (const uint64_t*)d_o, n_sets, total, d_rows, d_node)) != YH_OK) break;
+        const bool down_ok = hipMemcpyAsync(rows, d_rows, n_sets * sizeof(yh_classify_row), hipMemcpyDeviceToHost, db->stream) == hipSuccess &&
+                             (!node || !total || hipMemcpyAsync(node, d_node, total * sizeof(u32), hipMemcpyDeviceToHost, db->stream) == hipSuccess);
+        if (!down_ok || hipStreamSynchronize(db->stream) != hipSuccess) {
+            yh_set_error("classify download failed: %s", hipGetErrorString(hipGetLastError()));
+            rc = YH_ERR_HIP;
+        }
+    } while (0);
+    yh_tfree(db, d_s); yh_tfree(db, d_o); yh_tfree(db, d_out);
+    return rc;
+}
+
+// (YH_CLASSIFY_FIRST_CAP=n behind the tuning gate: the first capacity for kept hashes, so that a test can meet the sizing retry)
+int yh_classify_segments(yh_db* db, const uint8_t* seq, uint64_t n_bytes, const uint64_t* seg_off, uint64_t n_seg, int ksize,
+                         uint64_t seed, uint64_t max_hash, yh_classify_row* rows, uint64_t* n_kept_total) {
+    if (!db_ok(db)) return YH_ERR_INVALID_ARG;
+    if (!n_kept_total || !seg_off || (n_bytes && !seq) || (n_seg && !rows)) { yh_set_error("null argument"); return YH_ERR_INVALID_ARG; }
+    *n_kept_total = 0;
+    if (ksize < 1 || ksize > 255) { yh_set_error("ksize must be in [1, 255]"); return YH_ERR_INVALID_ARG; }
+    if (n_bytes >= (1ull << 32)) { yh_set_error("a segmented call takes less than 2^32 bytes"); return YH_ERR_INVALID_ARG; }
+    if (n_seg >= (1ull << 32)) { yh_set_error("a segmented call takes less than 2^32 segments"); return YH_ERR_INVALID_ARG; }
+    if (seg_off[0] != 0 || seg_off[n_seg] != n_bytes) { yh_set_error("segment offsets must start at 0 and end at n_bytes"); return YH_ERR_INVALID_ARG; }
+    for (u64 s = 0; s < n_seg; ++s)
+        if (seg_off[s] > seg_off[s + 1]) { yh_set_error("segment offsets must not descend (segment %llu)", s); return YH_ERR_INVALID_ARG; }
+    if (db->n_hashes && max_hash < db->max_hash) {
+        yh_set_error("max_hash %llu lies below the database's largest hash %llu: not the database's own", (u64)max_hash, (u64)db->max_hash);
+        return YH_ERR_INVALID_ARG;
+    }
+    if (n_seg == 0) return YH_OK;
+    YH_TRY(lca_supported(db));
+    YH_TRY(db_select(db));
+    YH_TRY(pipe_join(db));
+    // the copy stream and its events, per device, between calls (one call per process at a time, as yh_sketch_segments)
+    struct CsCtx { hipStream_t s_copy = nullptr; hipEvent_t ev[2] = {nullptr, nullptr}; hipEvent_t ev_free = nullptr; };
+    static std::mutex mu;
+    static CsCtx ctxs[64];
+    std::lock_guard<std::mutex> lock(mu);
+    CsCtx& c = ctxs[db->device & 63];
+    if (!c.s_copy) {
+        YH_HIP(hipStreamCreateWithFlags(&c.s_copy, hipStreamNonBlocking));
+        YH_HIP(hipEventCreateWithFlags(&c.ev[0], hipEventDisableTiming));
+        YH_HIP(hipEventCreateWithFlags(&c.ev[1], hipEventDisableTiming));
+        YH_HIP(hipEventCreateWithFlags(&c.ev_free, hipEventDisableTiming));
+    }
+    const bool hashes = n_bytes >= (u64)ksize;
+    const u64 n_win = hashes ? n_bytes - (u64)ksize + 1 : 0;
+    const double keep = ((double)max_hash + 1.0) / 18446744073709551616.0;
+    u64 cap_kept = std::min<u64>(n_win, (u64)((double)n_win * keep * 1.25) + 4096);
+    {
+        const long long first = yh_tune_int("YH_CLASSIFY_FIRST_CAP", 0);
+        if (first > 0) cap_kept = std::min<u64>(cap_kept, (u64)first);
+    }
+    u8 *d_seq = nullptr, *d_work = nullptr;
+    u64 *d_segoff = nullptr, *d_off = nullptr, *d_tot = nullptr, *d_mins = nullptr;
+    u32* d_abund = nullptr;
+    yh_classify_row* d_rows = nullptr;
+    u64 totals[2] = {0, 0};
+    int rc = YH_OK;
+    do {
+        if (yh_tmalloc(db, (void**)&d_seq, n_bytes + 64) != hipSuccess || yh_tmalloc(db, (void**)&d_segoff, (n_seg + 1) * sizeof(u64)) != hipSuccess ||
+            yh_tmalloc(db, (void**)&d_off, (n_seg + 1) * sizeof(u64)) != hipSuccess || yh_tmalloc(db, (void**)&d_tot, 2 * sizeof(u64)) != hipSuccess ||
+            yh_tmalloc(db, (void**)&d_rows, n_seg * sizeof(yh_classify_row)) != hipSuccess) {
+            (void)hipGetLastError(); yh_set_error("device allocation failed"); rc = YH_ERR_OOM; break;
+        }
+        if (hipMemcpyAsync(d_segoff, seg_off, (n_seg + 1) * sizeof(u64), hipMemcpyHostToDevice, db->stream) != hipSuccess) {
+            yh_set_error("classify upload failed"); rc = YH_ERR_HIP; break;
+        }
+        if (!hashes) {  // no window: every sketch is empty
+            if (hipMemsetAsync(d_off, 0, (n_seg + 1) * sizeof(u64), db->stream) != hipSuccess) { yh_set_error("classify clear failed"); rc = YH_ERR_HIP; break; }
+        }
+        // the cache hands a block out behind this point of the handle's stream: the copy stream starts there too
+        if (hipEventRecord(c.ev_free, db->stream) != hipSuccess || hipStreamWaitEvent(c.s_copy, c.ev_free, 0) != hipSuccess) {
+            yh_set_error("classify stream order failed"); rc = YH_ERR_HIP; break;
+        }
+        for (int pass = 0; hashes && pass < 2 && rc == YH_OK; ++pass) {
+            const u64 wb = yh_sketch_segments_work_bytes(cap_kept, n_seg);
+            yh_tfree(db, d_work); yh_tfree(db, d_mins); yh_tfree(db, d_abund);
+            d_work = nullptr; d_mins = nullptr; d_abund = nullptr;
+            if (wb == 0 || yh_tmalloc(db, (void**)&d_work, wb) != hipSuccess ||
+                yh_tmalloc(db, (void**)&d_mins, std::max<u64>(cap_kept, 2) * sizeof(u64)) != hipSuccess ||
+                yh_tmalloc(db, (void**)&d_abund, std::max<u64>(cap_kept, 4) * sizeof(u32)) != hipSuccess) {
+                (void)hipGetLastError(); yh_set_error("device allocation failed"); rc = YH_ERR_OOM; break;
+            }
+            if ((rc = yh_q_sketch_segments_hosted(seq, n_bytes, d_seq, (const u64*)d_segoff, (u32)n_seg, (u32)ksize, seed, max_hash, cap_kept, d_work,
+                                                  d_mins, d_abund, d_off, d_tot, db->stream, c.s_copy, c.ev, pass == 0)) != YH_OK) break;
+            if (hipMemcpyAsync(totals, d_tot, 2 * sizeof(u64), hipMemcpyDeviceToHost, db->stream) != hipSuccess ||
+                hipStreamSynchronize(db->stream) != hipSuccess) {
+                yh_set_error("classify sketch failed: %s", hipGetErrorString(hipGetLastError())); rc = YH_ERR_HIP; break;
+            }
+            if (totals[0] <= cap_kept) break;
+            if (pass == 1) { yh_set_error("kept hashes changed between two passes"); rc = YH_ERR_HIP; break; }
+            cap_kept = totals[0];
+        }
+        if (rc != YH_OK) break;
+        if ((rc = yh_classify_sets_device(db, (const uint64_t*)d_mins, (const uint64_t*)d_off, n_seg, totals[1], d_rows, nullptr)) != YH_OK) break;
+        if (hipMemcpyAsync(rows, d_rows, n_seg * sizeof(yh_classify_row), hipMemcpyDeviceToHost, db->stream) != hipSuccess ||
+            hipStreamSynchronize(db->stream) != hipSuccess) {
+            yh_set_error("classify download failed: %s", hipGetErrorString(hipGetLastError())); rc = YH_ERR_HIP; break;
+        }
+        *n_kept_total = totals[1];
+    } while (0);
+    if (rc != YH_OK) { (void)hipStreamSynchronize(c.s_copy); (void)hipStreamSynchronize(db->stream); }
+    yh_tfree(db, d_seq); yh_tfree(db, d_segoff); yh_tfree(db, d_off); yh_tfree(db, d_tot); yh_tfree(db, d_rows);
+    yh_tfree(db, d_work); yh_tfree(db, d_mins); yh_tfree(db, d_abund);
+    return rc;
 }
 
 // ---- the organism x sample tables of a cohort (yh_matrix.hip) ------------------------------------------------------------

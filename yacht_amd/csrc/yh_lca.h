@@ -1,4 +1,5 @@
-// yh_lca.h — the lowest-common-ancestor classification of sample hashes (yh_lca.hip) as yh_api.hip calls it.  Internal, like
+// yh_lca.h — the lowest-common-ancestor classification of sample hashes (yh_lca.hip) as yh_api.hip calls it, and the tree walk
+// its kernels share with the per-record fold (yh_classify.hip).  Internal, like
 // yh_common.h.
 #pragma once
 
@@ -16,6 +17,35 @@ struct YhTaxonomy {
     const u8* depth = nullptr;        // [n_nodes]
     u64 n_nodes = 0, bytes = 0;       // (0 nodes: no taxonomy set)
 };
+#if defined(__HIPCC__)
+// The LCA of nodes a and b: the deeper one lifted to the other's depth, then both lifted until they meet.  Every loop has
+// a fixed trip count with a break: the tree has passed the host's validation (depth <= YH_LCA_MAX_DEPTH, parent[v] < v), but
+// no input can make this spin.  Two nodes that have not met by then are not in one valid tree: the root.
+static __device__ __forceinline__ u32 lca_of(const u32* __restrict__ parent, const u8* __restrict__ depth, u32 a, u32 b) {
+    if (a == b) return a;
+    u32 da = depth[a], db = depth[b];
+#pragma unroll 1
+    for (int i = 0; i < YH_LCA_MAX_DEPTH; ++i) {
+        if (da <= db) break;
+        a = parent[a];
+        --da;
+    }
+#pragma unroll 1
+    for (int i = 0; i < YH_LCA_MAX_DEPTH; ++i) {
+        if (db <= da) break;
+        b = parent[b];
+        --db;
+    }
+#pragma unroll 1
+    for (int i = 0; i < YH_LCA_MAX_DEPTH; ++i) {
+        if (a == b) break;
+        a = parent[a];
+        b = parent[b];
+    }
+    return a == b ? a : 0u;
+}
+#endif
+
 // the handle's taxonomy (n_nodes == 0: none set)
 YhTaxonomy yh_lca_taxonomy(const yh_db* db);
 // Install `t` as the handle's taxonomy (null: remove it).  Returns the block of the one it replaces (or null) for the caller
@@ -41,3 +71,9 @@ int yh_q_lca_batch(yh_db* db, const YhTaxonomy& t, const u64* d_samples, const u
 // *d_n_rows (device): three launches, no host sync (include/yacht_hip.h: yh_lca_rows_pack_device).
 int yh_q_lca_rows_pack(yh_db* db, const YhTaxonomy& t, const u64* d_counts, u32 n_samples, yh_lca_row* d_rows, u64 cap_rows,
                        u64* d_n_rows);
+
+// One row per set of the CSR (d_mins, d_off[n_sets + 1]) under taxonomy `t` of the handle, and node [total] (d_node may be null),
+// enqueued on the handle's stream: a lookup launch over tiles of entries and a join launch (yh_classify.hip; include/yacht_hip.h:
+// yh_classify_sets_device).  The caller has checked the handle, its taxonomy, the pointers, n_sets (1 .. 2^32 - 1) and total.
+int yh_q_classify_sets(yh_db* db, const YhTaxonomy& t, const u64* d_mins, const u64* d_off, u64 n_sets, u64 total,
+                       yh_classify_row* d_rows, u32* d_node);

@@ -42,33 +42,6 @@ void* yh_lca_taxonomy_swap(const yh_db* db, const YhTaxonomy* t) {
 
 namespace {
 
-// The LCA of nodes a and b: the deeper one lifted to the other's depth, then both lifted until they meet.  Every loop has
-// a fixed trip count with a break: the tree has passed the host's validation (depth <= YH_LCA_MAX_DEPTH, parent[v] < v), but
-// no input can make this spin.  Two nodes that have not met by then are not in one valid tree: the root.
-__device__ __forceinline__ u32 lca_of(const u32* __restrict__ parent, const u8* __restrict__ depth, u32 a, u32 b) {
-    if (a == b) return a;
-    u32 da = depth[a], db = depth[b];
-#pragma unroll 1
-    for (int i = 0; i < YH_LCA_MAX_DEPTH; ++i) {
-        if (da <= db) break;
-        a = parent[a];
-        --da;
-    }
-#pragma unroll 1
-    for (int i = 0; i < YH_LCA_MAX_DEPTH; ++i) {
-        if (db <= da) break;
-        b = parent[b];
-        --db;
-    }
-#pragma unroll 1
-    for (int i = 0; i < YH_LCA_MAX_DEPTH; ++i) {
-        if (a == b) break;
-        a = parent[a];
-        b = parent[b];
-    }
-    return a == b ? a : 0u;
-}
-
 // One lane per shared hash: the LCA folded along its posting list, holders requested four at a time and their four leaf
 // words after them (as or_holders, yh_explain.hip).  The clamped tail re-reads the last holder: harmless, LCA is idempotent.
 // A fold that has reached the root leaves the list: nothing can lift it further -- which is what keeps a k-mer that

@@ -17,6 +17,7 @@
 // each segment, abund[] their run lengths, off[n_seg + 1] -- mins and off are exactly what yh_db_create_device takes as
 // d_values and d_offsets.
 #include "yh_common.h"
+#include "yh_sketch.h"
 
 #include <algorithm>
 #include <mutex>
@@ -810,6 +811,43 @@ extern "C" int yh_sketch_segments(const uint8_t* seq, uint64_t n_bytes, const ui
 #undef SK_HIP
     if (c.seq_cap > (1ull << 30)) { (void)hipFree(c.d_seq); c.d_seq = nullptr; c.seq_cap = 0; }
     return rc;
+}
+
+// The hashing and the finish of yh_sketch_segments on the caller's buffers and streams (yh_sketch.h): what yh_classify_segments
+// runs in front of the lookup, so that the sketches stay in HBM.  (yh_sketch_segments keeps its own loop over its own per-device
+// buffers: the two differ in who owns the buffers and the streams, not in the order of the steps.)
+int yh_q_sketch_segments_hosted(const u8* seq, u64 n_bytes, u8* d_seq, const u64* d_seg_off, u32 n_seg, u32 ksize, u64 seed, u64 max_hash,
+                                u64 cap_kept, void* d_work, u64* d_mins, u32* d_abund, u64* d_off, u64* d_totals, hipStream_t s_comp,
+                                hipStream_t s_copy, hipEvent_t ev[2], bool upload) {
+    SegWork w;
+    YH_TRY(seg_work_layout(cap_kept, w));
+    u8* work = reinterpret_cast<u8*>((reinterpret_cast<uintptr_t>(d_work) + 255u) & ~(uintptr_t)255u);
+    const SegArgs sa{d_seg_off, n_seg, (u32*)(work + w.seg_a)};
+    const u64 n_win = n_bytes - (u64)ksize + 1;
+    YH_HIP(hipMemsetAsync(d_totals, 0, 2 * sizeof(u64), s_comp));
+    if (cap_kept) YH_HIP(hipMemsetD32Async((hipDeviceptr_t)sa.out_seg, (int)n_seg, cap_kept, s_comp));
+    if (upload) {
+        const u64 piece = 32ull << 20;
+        u64 done_win = 0;
+        int flip = 0;
+        for (u64 p0 = 0; p0 < n_bytes; p0 += piece, flip ^= 1) {
+            const u64 p1 = std::min<u64>(n_bytes, p0 + piece);
+            YH_HIP(hipMemcpyAsync(d_seq + p0, seq + p0, p1 - p0, hipMemcpyHostToDevice, s_copy));
+            YH_HIP(hipEventRecord(ev[flip], s_copy));
+            YH_HIP(hipStreamWaitEvent(s_comp, ev[flip], 0));
+            // windows whose bytes are all there, in whole workgroups (the last piece: all that is left)
+            const u64 avail = p1 >= (u64)ksize ? p1 - (u64)ksize + 1 : 0;
+            const u64 upto = (p1 == n_bytes) ? n_win : (avail / SK_WIN_ALIGN) * SK_WIN_ALIGN;
+            if (upto > done_win) {
+                YH_TRY(launch_sketch(d_seq, p1, ksize, seed, max_hash, cap_kept, (u64*)(work + w.hash_a), d_totals, s_comp, done_win, upto, &sa));
+                done_win = upto;
+            }
+        }
+    } else {
+        YH_TRY(launch_sketch(d_seq, n_bytes, ksize, seed, max_hash, cap_kept, (u64*)(work + w.hash_a), d_totals, s_comp, 0, n_win, &sa));
+    }
+    return seg_finish(d_seq, n_bytes, d_seg_off, n_seg, ksize, seed, max_hash, cap_kept, work, w, cap_kept, d_mins, d_abund, d_off, d_totals,
+                      s_comp, true);
 }
 
 // ---- the accumulator: one sketch with abundances out of many chunks -----------------------------------------------------------

@@ -109,6 +109,8 @@ GATHER_ROW_DTYPE = np.dtype([("ref", np.uint32), ("n_overlap", np.uint32), ("n_u
                              ("w_unique", np.uint64)])
 # one row of RefDB.lca_rows_pack_device (include/yacht_hip.h: yh_lca_row)
 LCA_ROW_DTYPE = np.dtype([("sample", np.uint32), ("node", np.uint32), ("n_hashes", np.uint64), ("w_hashes", np.uint64)])
+# one row of RefDB.classify_sets (include/yacht_hip.h: yh_classify_row)
+CLASSIFY_ROW_DTYPE = np.dtype([("node", np.uint32), ("n_kept", np.uint32), ("n_hit", np.uint32), ("n_root", np.uint32)])
 # yh_matrix_cell: one (sample, reference) some coverage calls present; mask = one bit per coverage, depth2 = twice the median depth
 MATRIX_CELL_DTYPE = np.dtype([("sample", np.uint32), ("ref", np.uint32), ("n_match", np.uint32), ("mask", np.uint32), ("depth2", np.uint64)])
 
@@ -466,6 +468,49 @@ class RefDB:
             raise ValueError(f"cap_rows must be >= 0, not {cap_rows}")
         _lib.check(self._lib.yh_lca_rows_pack_device(self._h, C.c_void_p(d_counts), n_samples, C.c_void_p(d_rows), int(cap_rows),
                                                      C.c_void_p(d_n_rows)))
+
+    # ---- a taxon for every record (yh_classify.hip; yacht_amd.classify drives it) --------------------------------------------
+    def classify_sets(self, mins, off, want_nodes: bool = False):
+        """One row per set of the CSR (mins, off[n_sets + 1]) under the taxonomy set (yh_classify_sets): set s owns
+        mins[off[s]:off[s + 1]], strictly ascending inside the set.  Returns rows, a structured array of CLASSIFY_ROW_DTYPE
+        [n_sets]: node = the LCA of the set's informative hits (those whose node is neither _lib.YH_LCA_NONE nor the root), 0
+        with hits but none informative, YH_LCA_NONE without a hit; n_kept, n_hit, n_root the set's entries, those some
+        reference holds, and those that resolve to the root.  With want_nodes=True: (rows, nodes), nodes uint32 [len(mins)]
+        as RefDB.lca gives them for each set alone."""
+        mins = _as_u64(mins)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        if off.ndim != 1 or off.size < 1:
+            raise ValueError("off needs n_sets + 1 entries")
+        if int(off[-1]) != mins.size:
+            raise ValueError(f"off ends at {int(off[-1])}, mins holds {mins.size} entries")
+        rows = np.zeros(off.size - 1, dtype=CLASSIFY_ROW_DTYPE)
+        nodes = np.full(mins.size, _lib.YH_LCA_NONE, dtype=np.uint32) if want_nodes else None
+        _lib.check(self._lib.yh_classify_sets(self._h, _ptr(mins), _ptr(off), off.size - 1, _ptr(rows), _ptr(nodes)))
+        return (rows, nodes) if want_nodes else rows
+
+    def classify_sets_device(self, d_mins: int, d_off: int, n_sets: int, total: int, d_rows: int, d_node: int = 0) -> None:
+        """yh_classify_sets_device: uint64 mins and uint64 [n_sets + 1] offsets in (total: the host's copy of the last offset),
+        CLASSIFY_ROW_DTYPE [n_sets] rows and uint32 [total] nodes (0: none) out.  Does not synchronize the host."""
+        _lib.check(self._lib.yh_classify_sets_device(self._h, C.c_void_p(d_mins), C.c_void_p(d_off), int(n_sets), int(total),
+                                                     C.c_void_p(d_rows), C.c_void_p(d_node)))
+
+    def classify_segments(self, buf, seg_off, ksize: int, scaled: int, seed: int = 42, return_total: bool = False):
+        """One row of CLASSIFY_ROW_DTYPE per segment of `buf` (yh_classify_segments): every segment sketched as
+        sketch.sketch_segments does and its sketch classified as classify_sets does, with the sketches staying on the device.
+        seg_off [n_seg + 1]: ascending byte offsets from 0 to len(buf).  `scaled` must be the database's own: the caller
+        answers for it.  return_total=True: (rows, the entries of all sketches)."""
+        from .sketch import max_hash_for_scaled
+        if isinstance(buf, (bytes, bytearray, memoryview)):
+            buf = np.frombuffer(buf, dtype=np.uint8)
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        off = np.ascontiguousarray(seg_off, dtype=np.uint64)
+        if off.ndim != 1 or off.size < 1:
+            raise ValueError("seg_off needs n_seg + 1 entries")
+        rows = np.zeros(off.size - 1, dtype=CLASSIFY_ROW_DTYPE)
+        n = C.c_uint64(0)
+        _lib.check(self._lib.yh_classify_segments(self._h, _ptr(buf) if buf.size else None, buf.size, _ptr(off), off.size - 1, int(ksize),
+                                                  int(seed), max_hash_for_scaled(scaled), _ptr(rows), C.byref(n)))
+        return (rows, int(n.value)) if return_total else rows
 
     # ---- the organism x sample tables of a cohort (yh_matrix.hip; yacht_amd.matrix drives them) ----------------------------
     def matrix_cells_device(self, d_rows: int, d_n_rows: int, cap_rows: int, d_present: int, n_sets: int, d_med: int, sample_base: int,
